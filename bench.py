@@ -14,6 +14,12 @@ clip_grad_norm_(1) + Adam + zero_grad) as the fused HIP step -- kept inside the 
 no training work is skipped.  `--optimizer torch --dp ddp` runs the reference's own stack instead
 (torch.optim.Adam, DistributedDataParallel).  Inputs are resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (value, ms_per_step).  --full adds what is
+measured behind the timed region: the trunk chains live inside one more step (roofline.in_step_live), the dominant kernel's
+leg (roofline) and the CPU baseline (cpu_baseline; --no-cpu-baseline drops it).  --dump-outputs DIR writes, on rank 0, what
+the last timed step computed (loss, a seeded sample of sr, the updated trainable parameters and Adam's first moment, float32 /
+float64 .npy, < 64 MB in all); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -264,6 +270,36 @@ def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SR_SAMPLES = 1 << 20          # sr is 1.4 GB at two 540p clips: a seeded sample of it
+DUMP_MAX_ELEMS = 7_000_000         # per flat array (BasicVSR(64, 30) has 4.85 M trainable values, 6.29 M with train_flow)
+
+
+def dump_outputs(path, loss, sr, model, opt):
+    """What the last timed step handed its caller, as float .npy files under `path`: loss (float64), a fixed seeded sample of
+    sr, the updated trainable parameters and Adam's exp_avg (both flat, in model.parameters() order; seeded samples past
+    DUMP_MAX_ELEMS).  < 64 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def sample(x, k, seed):
+        x = x.reshape(-1)
+        if x.numel() <= k:
+            return x
+        idx = torch.randint(0, x.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+        return x[idx.to(x.device)]
+
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_m = torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in params])
+    arrays = {"loss": loss.detach().double().reshape(1),
+              "sr_sample": sample(sr, DUMP_SR_SAMPLES, 11),
+              "params": sample(flat_p, DUMP_MAX_ELEMS, 12),
+              "adam_exp_avg": sample(flat_m, DUMP_MAX_ELEMS, 12)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
+
+
 def cpu_baseline(h540, w540):
     """The oracle (CPU restatement of the reference, fp32, "port") on this box's host cores, on a bounded sample
     (BASELINE.md section 4): (i) BASELINE config 1 exactly (n=2, t=5, 64x64, rb=30) fwd+Charbonnier+bwd, best of 2
@@ -319,12 +355,18 @@ def main():
     ap.add_argument("--clips", type=int, default=2,
                     help="7-frame clips per GPU and step (BASELINE configs[1] '7-frame clips' / configs[3] 'batch-of-clips'; the reference's per-rank "
                          "micro-batch is 8 clips, conf/experiment/basic.yaml:10,25-26).  Two fit one 288 GB GPU in the full arena since round 4 "
-                         "(113 GiB per clip) and run ~2 % faster per frame than one (same kernels on twice the tiles per launch, the trunk chains "
+                         "(113 GiB per clip) and run ~2 %% faster per frame than one (same kernels on twice the tiles per launch, the trunk chains "
                          "image by image); --clips 1 is the round 1-3 workload")
     ap.add_argument("--arena", default="full", choices=["full", "diet"],
                     help="training workspace of the engine (VsrBasicVSRDesc.arena_mode): full = 113 GiB per clip, all-frames weight-gradient launches "
                          "(the headline configuration); diet = 65 GiB per clip (per-frame weight gradients, HR activations recomputed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs behind the timed region: roofline.in_step_live, the dominant kernel's leg, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (loss, sr sample, parameters, Adam exp_avg)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.optimizer == "torch" and args.dp == "flat":
         args.dp = "ddp"
 
@@ -387,7 +429,7 @@ def main():
     lrs = torch.rand(n, t, 3, h, w, generator=g).to(dev)
     hr = torch.rand(n, t, 3, 4 * h, 4 * w, generator=g).to(dev)
 
-    def step():
+    def step(keep_sr=False):
         sr = net(lrs)
         loss = crit(sr, hr)
         loss.backward()
@@ -395,7 +437,7 @@ def main():
             sync.all_reduce()
         opt.step()
         opt.zero_grad(set_to_none=(args.optimizer == "torch"))
-        return loss
+        return loss, (sr.detach() if keep_sr else None)
 
     for i in range(args.warmup):
         step()
@@ -405,9 +447,10 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
+    keep_last = args.dump_outputs is not None and rank == 0     # sr of the last step only: no step runs beside a kept one
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss, sr = step(keep_sr=keep_last and i == args.steps - 1)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -420,6 +463,9 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     if rank == 0:
         log(f"timed region: {ms_per_step:.1f} ms/step")
+        if keep_last:
+            dump_outputs(args.dump_outputs, loss, sr, model, opt)
+            del sr
     frames_per_s = world * n * t * args.steps / elapsed
 
     if rank == 0:
@@ -448,15 +494,16 @@ def main():
                                 "achieved_GBs_per_gpu": round(bpf * frames_per_s / world / 1e9, 1),
                                 "hbm_frac": round(bpf * frames_per_s / world / 1e9 / HBM_PEAK_GBS, 4),
                                 "achieved_TFLOPs_per_gpu": round(fpf * frames_per_s / world / 1e12, 1)}
-        # (not under stock DDP at world > 1: a backward outside its forward would meet the reducer's hooks)
-        live = chains_in_step_live(model, crit, lrs, hr, opt, args) if args.dtype == "bf16" and (world == 1 or sync is not None) else None
-        if args.dtype == "bf16":                             # the dominant kernel's leg: rank 0's GPU, after the timed region, at every N
-            out["roofline"] = dominant_kernel_roofline(dev, h, w)
-            log(f"dominant kernel: {out['roofline']['avg_us']} us")
-            if live is not None:
-                out["roofline"]["in_step_live"] = live
-        if world == 1 and not args.no_cpu_baseline:          # the CPU baseline: rank 0 at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(h, w)
+        if args.full:
+            # (not under stock DDP at world > 1: a backward outside its forward would meet the reducer's hooks)
+            live = chains_in_step_live(model, crit, lrs, hr, opt, args) if args.dtype == "bf16" and (world == 1 or sync is not None) else None
+            if args.dtype == "bf16":                             # the dominant kernel's leg: rank 0's GPU, after the timed region, at every N
+                out["roofline"] = dominant_kernel_roofline(dev, h, w)
+                log(f"dominant kernel: {out['roofline']['avg_us']} us")
+                if live is not None:
+                    out["roofline"]["in_step_live"] = live
+            if world == 1 and not args.no_cpu_baseline:          # the CPU baseline: rank 0 at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(h, w)
         print(json.dumps(out), flush=True)
     if dist:
         # ranks 1..N-1 wait here while rank 0 runs its post-timing legs (in_step_live, the dominant kernel's leg) on its GPU:

@@ -4,7 +4,7 @@
     python profiles/summarize.py gpurun_out/r2p r02
 
 Inputs (all produced by the commands listed in profiles/README.md, program directly after `--`):
-  trace2s/ , trace1s/ : rocprofv3 --kernel-trace --stats  -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+  trace2s/ , trace1s/ : rocprofv3 --kernel-trace --stats  -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
                         (default two-stream engine / VSRLAB_AMD_SINGLE_STREAM=1)
   pmc_fetch/, pmc_write/, pmc_mfma/ : rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --roofline-only
 Outputs: <tag>_bench_kernel_stats.csv (two-stream), <tag>_bench_kernel_stats_single_stream.csv, <tag>_roofline.json.
@@ -68,7 +68,7 @@ def main():
             out["in_kernel_clock_GHz"] = float(m[-1])
     except OSError:
         pass
-    # ---- roofline leg: its 12 timed launches are the last 12 chain rows of any trace of bench.py; the one-launch-per-layer leg
+    # ---- roofline leg: its 12 timed launches are the last 12 chain rows of any trace of bench.py --full; the one-launch-per-layer leg
     # behind it is the last 48 persistent-conv rows ----
     allrows = list(rows(os.path.join(src, "trace1s", "bench_kernel_trace.csv")))
     us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
@@ -107,7 +107,7 @@ def main():
             mf["clock_GHz_used"] = ghz
         out["mfma_busy"] = mf
     # ---- the same kernel inside ONE timed step (single-stream trace: no overlap inflating durations) ----
-    # bench.py --steps 1 --warmup 1: the trace holds 2 steps (per step 14 forward chains <0> of 60 layers and 14 backward chains <2>
+    # bench.py --full --steps 1 --warmup 1: the trace holds 2 steps (per step 14 forward chains <0> of 60 layers and 14 backward chains <2>
     # of 59), then the roofline leg (2 warm + 12 timed launches of <0>)
     fw = [r for r in tr if "<0>" in r["Kernel_Name"]][:-(CHAIN_ITERS + 2)]
     bw = [r for r in tr if "<2>" in r["Kernel_Name"]]
@@ -121,7 +121,7 @@ def main():
            "backward chain <CHAIN_MASK>, 59 layers": {"launches": len(bw), "avg_us": round(tb / max(len(bw), 1), 1), "avg_us_per_layer": round(tb / max(len(bw), 1) / 59, 2)}}
     out["in_step"] = {"what": "the trunk chains of conv3x3_c64_chain_kernel inside one timed step (single-stream trace), call-weighted",
                       "per_variant": per, "algorithmic_GBs": round(tot_b / tot_t / 1e3, 1), "frac_of_8TBs": round(tot_b / tot_t / 1e3 / 8000.0, 4)}
-    # ---- HBM bytes of the dominant kernels INSIDE a step (r04): FETCH_SIZE / WRITE_SIZE passes over `bench.py --clips 1 --steps 1 --warmup 1`
+    # ---- HBM bytes of the dominant kernels INSIDE a step (r04): FETCH_SIZE / WRITE_SIZE passes over `bench.py --full --clips 1 --steps 1 --warmup 1`
     # (pmc_step_fetch/, pmc_step_write/), per launch, against the algorithmic bytes of the same launch.  In the step a layer's input was
     # written one layer earlier: what the counters show below the algorithmic read bytes is served by the 256 MiB Infinity Cache. ----
     try:
@@ -155,7 +155,7 @@ def main():
 
 
 def lds_conflicts(src, tag, here, sha1, head):
-    """<tag>_lds_conflicts.md from pmc_lds/ (rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -- python3 bench.py
+    """<tag>_lds_conflicts.md from pmc_lds/ (rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -- python3 bench.py --full
     --train-flow --clips 1 --steps 1 --warmup 1 --no-cpu-baseline): conflict cycles / active cycles per kernel, summed over its launches.
     Stamped with the profiled tree's csrc_sha1 (round-3 VERDICT #11: a stale file under a "final tree" heading)."""
     path = os.path.join(src, "pmc_lds", "lds_counter_collection.csv")
@@ -174,7 +174,7 @@ def lds_conflicts(src, tag, here, sha1, head):
         k = r["Kernel_Name"]
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
         launches[k].add(r["Dispatch_Id"])
-    lines = [f"# LDS bank conflicts per kernel over `bench.py --train-flow --clips 1 --steps 1 --warmup 1` under rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE",
+    lines = [f"# LDS bank conflicts per kernel over `bench.py --full --train-flow --clips 1 --steps 1 --warmup 1` under rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE",
              f"# profiled tree: csrc_sha1 {tree.get('csrc_sha1')}, git {tree.get('git_head')} (written by profiles/summarize.py {tag}; regenerate with profiles/{tag}_commands.sh)",
              "", "| kernel | launches | SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE |", "|---|---|---|"]
     for k in sorted(acc):

@@ -450,3 +450,38 @@ def test_chain_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert lib.vsr_conv3x3_c64_chain_fwd(None, None, None, 2, 1, 8, 8, None, None) == -1
     # misaligned operands: refused (offsets are in units of 256 bytes from one base), before any launch
     assert lib.vsr_conv3x3_c64_chain_fwd(0x10000100, 0x20000000, 0x30000010, 2, 1, 8, 8, 0x40000000, None) == -2
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss (float64), a seeded sample of sr and the flat trainable parameters / Adam exp_avg (float32),
+    full below the element caps and the same seeded sample on every call above them; the headline configuration stays < 64 MB."""
+    import numpy as np
+    import bench
+    # BasicVSR(64, 30) with train_flow: 6.29 M trainable values, plus the sr sample and the loss
+    assert (bench.DUMP_SR_SAMPLES + 2 * min(6_291_311, bench.DUMP_MAX_ELEMS)) * 4 + 8 < 64e6
+    from vsrlab_amd.vsr.models.RealBasicVSR.modules.basicvsr import BasicVSR
+    torch.manual_seed(0)
+    m = BasicVSR(16, 2, 4, False, False)
+    params = [p for p in m.parameters() if p.requires_grad]
+    opt = torch.optim.Adam(params, lr=1e-4)
+    for p in params:
+        p.grad = torch.randn_like(p)
+    opt.step()
+    sr = torch.rand(1, 3, 3, 512, 512)                   # 2.4 M values > DUMP_SR_SAMPLES
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_m = torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in params])
+
+    def dump(d):
+        bench.dump_outputs(str(d), torch.tensor(0.25), sr, m, opt)
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    a = dump(tmp_path / "a")
+    assert sorted(a) == ["adam_exp_avg", "loss", "params", "sr_sample"]
+    assert a["loss"].dtype == np.float64 and a["loss"].tolist() == [0.25]
+    assert all(a[k].dtype == np.float32 for k in ("adam_exp_avg", "params", "sr_sample"))
+    assert a["sr_sample"].shape == (bench.DUMP_SR_SAMPLES,) and np.isin(a["sr_sample"], sr.numpy()).all()
+    assert np.array_equal(a["params"], flat_p.numpy()) and np.array_equal(a["adam_exp_avg"], flat_m.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    b, c = dump(tmp_path / "b"), dump(tmp_path / "c")
+    assert b["params"].shape == (1000,) and np.isin(b["params"], flat_p.numpy()).all()
+    assert all(np.array_equal(b[k], c[k]) for k in b) and np.array_equal(a["sr_sample"], b["sr_sample"])

@@ -47,7 +47,9 @@ const char* vsr_status_string(int status);
 
 /* ---- whole-path engine -------------------------------------------------------------------
  * Replaces BasicVSR.forward and its autograd backward (basicvsr.py:39-83).
- * mid_channels must be 64 (the reference's default, basicvsr.py:12-13); upscale 4 (default: two
+ * mid_channels must be 64 (the reference's default, basicvsr.py:12-13) for the vsr_basicvsr_* entries; the
+ * narrow widths 16 and 32 have an entry family of their own (vsr_basicvsr_narrow_*, below: same descriptor,
+ * same contract, 64 rejected there), so that each width has exactly one way in; upscale 4 (default: two
  * PixelShufflePacks, x4 bilinear skip) or 2 (ONE PixelShufflePack = upscale // 2, conv_last at 2h x 2w,
  * x2 bilinear skip: basicvsr.py:19-22; conf/train/model/basicvsr.yaml:4 takes the scale from the dataset
  * config); res_blocks >= 1; t <= 32 (test.py's window).  A trunk-chain launch that gave up a dependency
@@ -106,6 +108,20 @@ int vsr_basicvsr_backward(const VsrBasicVSRDesc* d, const float* const* params, 
 int vsr_basicvsr_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward,
                            float* flow_backward, void* stream);
 
+/* The same four entries for mid_channels 16 or 32 (BasicVSR(16, ...), the reference's ablation widths; every other
+ * width returns 0 bytes / VSR_STATUS_UNSUPPORTED).  Parameter order, need_backward, arena_mode, grads and dlrs as above.
+ * Every layer is one generic implicit-GEMM launch (no trunk chains, no persistent kernels); the data gradients take their
+ * ReLU / LeakyReLU masks from the stored activations.  conv_last.0 still outputs 64 channels (basicvsr.py:20).        */
+size_t vsr_basicvsr_narrow_workspace_bytes(const VsrBasicVSRDesc* d, int need_backward);
+int vsr_basicvsr_narrow_forward(const VsrBasicVSRDesc* d, const float* const* params, int nparams,
+                                const float* lrs, float* sr, void* workspace, size_t workspace_bytes,
+                                int need_backward, void* stream);
+int vsr_basicvsr_narrow_backward(const VsrBasicVSRDesc* d, const float* const* params, float* const* grads,
+                                 int nparams, const float* lrs, const float* dsr, float* dlrs, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int vsr_basicvsr_narrow_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward,
+                                  float* flow_backward, void* stream);
+
 /* ---- SPyNet alone: flow = Spynet(ref, supp)  (RealBasicVSR/modules/spynet.py:69-93) -------
  * ref/supp (N,3,h,w) fp32 planar; params: the 62 spynet tensors in state_dict order.        */
 size_t vsr_spynet_workspace_bytes(int N, int h, int w, int dtype, int need_backward);
@@ -140,6 +156,10 @@ int vsr_spynet_backward_ex(int N, int h, int w, int dtype, const float* const* p
  * bias}, resblock.res_block.{i}.conv1.{weight,bias}, conv2.{weight,bias} ..., conv.{weight,bias}.
  * lq is a fresh tensor (the reference updates lr in place: SURVEY.md appendix A3).             */
 size_t vsr_cleaner_workspace_bytes(int F, int h, int w, int blocks, int steps, int dtype, int need_backward);
+/* Workspace of the pre-clean stack at mid_channels 16 or 32 (0 for any other width): vsr_cleaner_forward / _backward
+ * accept those widths with a workspace of this size (and 64 with one of vsr_cleaner_workspace_bytes).                */
+size_t vsr_cleaner_narrow_workspace_bytes(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype,
+                                          int need_backward);
 int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype,
                         const float* const* params, int nparams, const float* lr, float* lq,
                         void* workspace, size_t workspace_bytes, int need_backward, void* stream);
@@ -209,9 +229,9 @@ int vsr_conv3x3_c64_dgrad(int dtype, const void* dy_pm, const float* w, void* wp
 /* One convolution layer (forward; its backward is vsr_conv_layer_bwd below), for the building blocks the reference's modules expose on their own: ConvReLU
  * (core/modules/conv.py:15-22), SpynetModule (spynet.py:13-21), PixelShufflePack (upsampling.py:4-12), the stem of
  * ResidualBlock (conv.py:97).  w fp32 OIHW, b fp32 or NULL.
- *   ks 3 / 1: 64 -> 64 (pixel_shuffle != 0: 64 -> 256 written as (N,2H,2W,64));
+ *   ks 3 / 1: C -> C for C = 16, 32 or 64 (pixel_shuffle != 0: C -> 4C written as (N,2H,2W,C));
  *   ks 7    : (cin_pm, cout_real) in {(16,32), (32,64), (64,32), (32,16), (16,2: y_planar)} with cin_real = 8,32,64,32,16;
- *   lr_planar (N,3,H,W), ks 3: the conv reads cat([lr, x_pm]) (cin_real 67) or lr alone (x_pm NULL, cin_real 3).
+ *   lr_planar (N,3,H,W), ks 3: the conv reads cat([lr, x_pm]) (cin_real C + 3) or lr alone (x_pm NULL, cin_real 3); C = cout_real.
  * y_pm: cd channels per pixel; y_planar (N,cout_real,H,W) for cout_real <= 4.  wpack: scratch, 49*64*64*4 elements.   */
 int vsr_conv_layer_fwd(int dtype, int ks, const void* x_pm, int cin_pm, const float* lr_planar, const float* w,
                        const float* b, int cin_real, int cout_real, void* wpack, void* y_pm, int cd, float* y_planar,

@@ -41,12 +41,17 @@ _SIGNATURES = {
     "vsr_basicvsr_forward": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, c_int, _P, _P, _P, c_size_t, c_int, _P]),
     "vsr_basicvsr_backward": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "vsr_basicvsr_get_flows": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, _P, _P, _P]),
+    "vsr_basicvsr_narrow_workspace_bytes": (c_size_t, [ctypes.POINTER(BasicVSRDesc), c_int]),
+    "vsr_basicvsr_narrow_forward": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, c_int, _P, _P, _P, c_size_t, c_int, _P]),
+    "vsr_basicvsr_narrow_backward": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_basicvsr_narrow_get_flows": (c_int, [ctypes.POINTER(BasicVSRDesc), _P, _P, _P, _P]),
     "vsr_spynet_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "vsr_spynet_forward": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, c_int, _P]),
     "vsr_spynet_backward": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P]),
     "vsr_spynet_forward_ex": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_size_t, c_int, _P]),
     "vsr_spynet_backward_ex": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "vsr_cleaner_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vsr_cleaner_narrow_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "vsr_cleaner_forward": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_size_t, c_int, _P]),
     "vsr_cleaner_backward": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "vsr_flow_warp_fwd": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),

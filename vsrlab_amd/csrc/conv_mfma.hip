@@ -479,7 +479,24 @@ int launch_inst(const ConvArgs& a, hipStream_t st) {
     X(7, 1, 32, 32, false, 64, EPI_NHWC)    /* SPyNet 32->64                                    */ \
     X(7, 1, 64, 64, false, 32, EPI_NHWC)    /* SPyNet 64->32 ; 32->16 uses (7,1,32,32,..,32)    */ \
     X(7, 1, 32, 32, false, 32, EPI_NHWC)    \
-    X(7, 1, 16, 16, false, 32, EPI_PLANAR)  /* SPyNet 16->2 (+ReLU) + flow_up residual          */
+    X(7, 1, 16, 16, false, 32, EPI_PLANAR)  /* SPyNet 16->2 (+ReLU) + flow_up residual          */ \
+    /* mid_channels C = 16 / 32 (the narrow engine): C outputs on the 32-row template (cout_real = C) */ \
+    X(3, 1, 16, 16, false, 32, EPI_NHWC)    /* trunk / upsample (nz = 4) and their dgrads, C=16 */ \
+    X(3, 1, 32, 32, false, 32, EPI_NHWC)    /* ... C=32                                         */ \
+    X(3, 2, 16, 16, true, 32, EPI_NHWC)     /* trunk stem on cat(lr_i, feat), C=16              */ \
+    X(3, 2, 32, 16, true, 32, EPI_NHWC)     /* ... C=32                                         */ \
+    X(3, 1, 16, 16, true, 32, EPI_NHWC)     /* cleaner stem 3->C, dgrad of the cleaner out conv */ \
+    X(1, 2, 16, 16, false, 32, EPI_NHWC)    /* point_conv 2C->C                                 */ \
+    X(1, 2, 32, 32, false, 32, EPI_NHWC)    \
+    X(1, 1, 16, 16, false, 32, EPI_NHWC)    /* its dgrad (two C-channel outputs)                */ \
+    X(1, 1, 32, 32, false, 32, EPI_NHWC)    \
+    X(3, 4, 16, 16, false, 32, EPI_NHWC)    /* dgrad of conv3x3 C->4C + PixelShuffle(2)         */ \
+    X(3, 4, 32, 32, false, 32, EPI_NHWC)    \
+    X(3, 1, 16, 16, false, 64, EPI_NHWC)    /* conv_last.0 C->64 at HR                          */ \
+    X(3, 1, 32, 32, false, 64, EPI_NHWC)    \
+    X(3, 1, 64, 64, false, 32, EPI_NHWC)    /* its dgrad 64->C (cout_real = C)                  */ \
+    X(3, 1, 16, 16, false, 32, EPI_PLANAR)  /* C->3 planar: cleaner out conv, stems' LR dgrad   */ \
+    X(3, 1, 32, 32, false, 32, EPI_PLANAR)
 
 int vsr_launch_conv3x3_c64_persist(const ConvArgs& a, int num_cus, hipStream_t st);
 int vsr_launch_c64_to_planar(const ConvArgs& a, hipStream_t st);      // hr_tail.hip

@@ -154,11 +154,12 @@ __device__ __forceinline__ bool flow_is_far(float fx, float fy) {
     return !(fabsf(fx) <= (float)(GR - 1) && fabsf(fy) <= (float)(GR - 1));      // NaN counts as far
 }
 
-template <typename T>
+// C: channels (16, 32, 64); phase 2 serves 256 / (C / 8) destination pixels per pass with C / 8 lanes (chunks) each
+template <typename T, int C>
 __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const T* __restrict__ dout, const float* __restrict__ flow, const T* __restrict__ dtop,
                                                               long long* __restrict__ S, const int* __restrict__ far_count, T* __restrict__ out,
                                                               int N, int H, int W, long long flow_nstride) {
-    constexpr int C = 64;
+    constexpr int CP = C / 8, PPP = 256 / CP;          // chunks per pixel, destination pixels per pass
     typedef typename EW<T>::chunk_t chunk_t;
     __shared__ float2 pos[GHH * GHW];                   // sample position of each source of the haloed tile; x = NaN: far / outside
     __shared__ unsigned short hit_src[256 * GCAP];
@@ -206,9 +207,9 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const T* __restric
     const int far_n = far_count[0];
     const bool add_far = far_n != 0;
     const bool far_bad = (far_n & FAR_BAD) != 0;        // a far contribution was not representable (NaN / Inf / huge cotangent)
-    const int c = tid & 7;
-    for (int pass = 0; pass < 8; ++pass) {              // phase 2: 32 destination pixels per pass, 8 lanes (chunks) each
-        const int d = pass * 32 + (tid >> 3);
+    const int c = tid % CP;
+    for (int pass = 0; pass < CP; ++pass) {             // phase 2: PPP destination pixels per pass, CP lanes (chunks) each
+        const int d = pass * PPP + tid / CP;
         const int dy = d >> 5, dx = d & 31;
         const int yi = ty0 + dy, xi = tx0 + dx;
         if (yi >= H || xi >= W) continue;
@@ -264,10 +265,9 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const T* __restric
 }
 
 // the "far" sources of the gather form: |flow| > GR - 1 (or non-finite): scattered with atomics like warp_bwd_kernel, and counted
-template <typename T>
+template <typename T, int C>
 __global__ void warp_bwd_far_kernel(const T* __restrict__ dout, const float* __restrict__ flow, long long* __restrict__ S, int* __restrict__ far_count,
                                     int N, int H, int W, long long flow_nstride) {
-    constexpr int C = 64;
     const long long total = (long long)N * H * W;
     const int lane = threadIdx.x & 63;
     // a wave scans 64 consecutive pixels (one flow vector per lane, coalesced) and then serves the far ones among them -- usually none --
@@ -290,6 +290,7 @@ __global__ void warp_bwd_far_kernel(const T* __restrict__ dout, const float* __r
         const float fx = __shfl(mfx, b, 64), fy = __shfl(mfy, b, 64);
         const int c = threadIdx.x & 63;
         if (c == 0) atomicAdd(far_count, 1);
+        if (c >= C) continue;                           // C < 64: lanes C..63 have no channel
         const float px = warp_coord((float)x, fx, W), py = warp_coord((float)y, fy, H);
         if (!(px == px && py == py)) continue;
         const float fx0 = floorf(px), fy0 = floorf(py);
@@ -892,21 +893,29 @@ int vsr_launch_warp_bwd(int dtype, const void* dout, const float* flow, float* d
     return VSR_OK;
 }
 
-// out = T(dtop + warp^T(dout)) for the 64-channel propagation warps (zeros padding): gather kernel + far-source scatter.
-// S: fp32 [N][H][W][64], ALL ZERO on entry and on exit; far_count: one int, zero on entry (the number of far sources on exit).
-int vsr_launch_warp_bwd_gather(int dtype, const void* dout, const float* flow, const void* dtop, long long* S, int* far_count, void* out,
-                               int N, int H, int W, long long flow_nstride, hipStream_t st) {
-    if (!dout || !flow || !S || !far_count || !out) return VSR_ERR_BADARG;
+// out = T(dtop + warp^T(dout)) for the C-channel propagation warps (zeros padding, C = 16, 32 or 64): gather kernel + far-source scatter.
+// S: 64-bit fixed point [N][H][W][C], ALL ZERO on entry and on exit; far_count: one int, zero on entry (the number of far sources on exit).
+template <int C>
+static int warp_bwd_gather_c(int dtype, const void* dout, const float* flow, const void* dtop, long long* S, int* far_count, void* out,
+                             int N, int H, int W, long long flow_nstride, hipStream_t st) {
     const long long npix = (long long)N * H * W;
     const int tiles = N * cdiv(H, GTH) * cdiv(W, GTW);
     long long gb = (npix + 255) / 256;                      // 4 waves per block x 64 pixels per wave
     if (gb > 256 * 16) gb = 256 * 16;
     if (gb < 1) gb = 1;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(warp_bwd_far_kernel<T>, dim3((int)gb), dim3(256), 0, st, (const T*)dout, flow, S, far_count, N, H, W, flow_nstride));
-    DISPATCH_T(dtype, hipLaunchKernelGGL(warp_bwd_gather_kernel<T>, dim3(tiles), dim3(256), 0, st, (const T*)dout, flow, (const T*)dtop, S,
+    DISPATCH_T(dtype, hipLaunchKernelGGL((warp_bwd_far_kernel<T, C>), dim3((int)gb), dim3(256), 0, st, (const T*)dout, flow, S, far_count, N, H, W, flow_nstride));
+    DISPATCH_T(dtype, hipLaunchKernelGGL((warp_bwd_gather_kernel<T, C>), dim3(tiles), dim3(256), 0, st, (const T*)dout, flow, (const T*)dtop, S,
                                          (const int*)far_count, (T*)out, N, H, W, flow_nstride));
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
+}
+int vsr_launch_warp_bwd_gather(int dtype, const void* dout, const float* flow, const void* dtop, long long* S, int* far_count, void* out,
+                               int N, int H, int W, int C, long long flow_nstride, hipStream_t st) {
+    if (!dout || !flow || !S || !far_count || !out) return VSR_ERR_BADARG;
+    if (C == 64) return warp_bwd_gather_c<64>(dtype, dout, flow, dtop, S, far_count, out, N, H, W, flow_nstride, st);
+    if (C == 32) return warp_bwd_gather_c<32>(dtype, dout, flow, dtop, S, far_count, out, N, H, W, flow_nstride, st);
+    if (C == 16) return warp_bwd_gather_c<16>(dtype, dout, flow, dtop, S, far_count, out, N, H, W, flow_nstride, st);
+    return VSR_ERR_UNSUPPORTED;
 }
 
 int vsr_launch_add_cast(int dtype, const void* a, const float* s, void* out, int N, int H, int W, int C, hipStream_t st) {

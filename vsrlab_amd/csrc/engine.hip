@@ -23,7 +23,7 @@ struct Bump {
 
 inline size_t esize(int dtype) { return dtype == VSR_BF16 ? 2 : 4; }
 
-constexpr int C = 64;           // mid channels of the HIP path
+constexpr int C = 64;           // mid channels of the HIP path (the narrow entries run 16 / 32: Plan::C shadows this in the engine)
 constexpr int NSPY = 5;         // convs per SPyNet level
 const int SPY_CI[NSPY] = {8, 32, 64, 32, 16}, SPY_CO[NSPY] = {32, 64, 32, 16, 2};
 const int SPY_CIP[NSPY] = {16, 32, 64, 32, 16}, SPY_COP[NSPY] = {32, 64, 32, 32, 32};   // padded (template) sizes
@@ -85,6 +85,11 @@ struct SpyPlan {
 
 struct Plan {
     VsrBasicVSRDesc d;
+    // mid channels: 64 (the whole-path entries: chains, persistent kernels, sign bits, phase planes) or 16 / 32 (the narrow entries:
+    // one generic-kernel launch per layer, ReLU / LeakyReLU masks of the data gradients from the stored activations); CO: the conv
+    // template's output rows for C outputs (C = 16 runs on the 32-row template with cout_real = 16)
+    int C = 64, CO = 64;
+    bool sb = false;             // sign bits of the masked data gradients are kept (bf16 training at C = 64)
     bool bwd, flowgrad;          // flowgrad: train_flow (basicvsr.py:25-28), SPyNet is differentiated too
     bool diet;                   // VsrBasicVSRDesc.arena_mode = 1 (training only): see vsrlab_hip.h
     int rb, n, t, h, w, dtype;
@@ -136,33 +141,39 @@ struct Plan {
     size_t g1off(int dir, int i, int b) const { return diet ? G1[dir][b & 1] : G1[dir][(size_t)i * rb + b]; }
     size_t dxoff(int dir, int i, int b) const { return diet ? DX[dir][b & 1] : DX[dir][(size_t)i * (rb + 1) + b]; }
 
-    int build(const VsrBasicVSRDesc& desc, int mode) {     // 0 inference, 1 training (frozen flow), 2 training incl. SPyNet
+    int build(const VsrBasicVSRDesc& desc, int mode, bool narrow = false) {     // mode: 0 inference, 1 training (frozen flow), 2 training incl. SPyNet
         d = desc; bwd = mode >= 1; flowgrad = mode >= 2;
         { const char* e = getenv("VSRLAB_AMD_CHAIN"); chain_mode = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
         if (d.arena_mode != 0 && d.arena_mode != 1) return VSR_ERR_BADARG;
         diet = bwd && d.arena_mode == 1;
         rb = d.res_blocks; n = d.n; t = d.t; h = d.h; w = d.w; dtype = d.dtype;
         scale = d.upscale; ups = scale / 2; unsh = false;
-        if (d.mid_channels != C || (scale != 4 && scale != 2) || rb < 1 || n < 1 || t < 1 || t > 32 || h < 1 || w < 1) return VSR_ERR_UNSUPPORTED;
+        const bool width_ok = narrow ? (d.mid_channels == 16 || d.mid_channels == 32) : d.mid_channels == 64;
+        if (!width_ok || (scale != 4 && scale != 2) || rb < 1 || n < 1 || t < 1 || t > 32 || h < 1 || w < 1) return VSR_ERR_UNSUPPORTED;
         if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
+        const int C = d.mid_channels;
+        this->C = C; CO = C < 32 ? 32 : C;
+        sb = bwd && dtype == VSR_BF16 && C == 64;
         es = esize(dtype);
         px1 = (size_t)n * pm_image_elems(h, w, C);
         s_elems = (size_t)n * h * w * C;
-        // a2: a blocked 64-channel tensor at 2h x 2w; a4: at the output size scale h x scale w (= a2 for upscale 2, which has no U1)
+        // a2: a blocked C-channel tensor at 2h x 2w; a4: at the output size scale h x scale w (= a2 for upscale 2, which has no U1);
+        // a4h: conv_last.0's 64-channel output (and its gradient) at the output size (= a4 at C = 64)
         const size_t a2 = (size_t)n * pm_image_elems(2 * h, 2 * w, C) * es, a4 = (size_t)n * pm_image_elems(scale * h, scale * w, C) * es;
+        const size_t a4h = (size_t)n * pm_image_elems(scale * h, scale * w, 64) * es;
         Bump b;
-        const size_t w64 = (size_t)9 * C * C * es;
+        const size_t w64 = (size_t)9 * CO * C * es;
         for (int dir = 0; dir < 2; ++dir) {
-            stem_w[dir] = b.take(w64 + (size_t)9 * C * 16 * es);
+            stem_w[dir] = b.take(w64 + (size_t)9 * CO * 16 * es);
             stem_wd[dir] = b.take(w64);
             stem_b[dir] = b.take(C * 4);
             blk_w[dir].resize(2 * rb); blk_wd[dir].resize(2 * rb); blk_b[dir].resize(2 * rb);
             for (int k = 0; k < 2 * rb; ++k) { blk_w[dir][k] = b.take(w64); blk_wd[dir][k] = b.take(w64); blk_b[dir][k] = b.take(C * 4); }
         }
-        point_w = b.take((size_t)2 * C * C * es); point_wd = b.take((size_t)2 * C * C * es); point_b = b.take(C * 4);
+        point_w = b.take((size_t)2 * CO * C * es); point_wd = b.take((size_t)2 * CO * C * es); point_b = b.take(C * 4);
         for (int k = 0; k < 2; ++k) { up_w[k] = b.take(4 * w64); up_wd[k] = b.take(4 * w64); up_b[k] = b.take(4 * C * 4); }
-        last0_w = b.take(w64); last0_wd = b.take(w64); last0_b = b.take(C * 4);
-        last2_w = b.take((size_t)9 * 32 * C * es); last2_wd = b.take((size_t)9 * C * 16 * es); last2_b = b.take(64 * 4);
+        last0_w = b.take((size_t)9 * 64 * C * es); last0_wd = b.take((size_t)9 * CO * 64 * es); last0_b = b.take(64 * 4);
+        last2_w = b.take((size_t)9 * 32 * 64 * es); last2_wd = b.take((size_t)9 * 64 * 16 * es); last2_b = b.take(64 * 4);
         if (t > 1) spy.plan(b, 2 * n * (t - 1), n * t, h, w, dtype);
         flows = b.take((size_t)2 * n * (t > 1 ? t - 1 : 1) * 2 * h * w * 4);
         const size_t a1 = px1 * es;
@@ -171,7 +182,7 @@ struct Plan {
             if (bwd) {
                 X[dir].assign((size_t)t * (rb + 1), 0); A[dir].assign((size_t)t * rb, 0); SB[dir].assign((size_t)t * rb, 0);
                 SBX0[dir].assign(t, 0);
-                const size_t sbytes = dtype == VSR_BF16 ? (size_t)n * cdiv(h, 8) * cdiv(w, 32) * 2048 : 256;
+                const size_t sbytes = sb ? (size_t)n * cdiv(h, 8) * cdiv(w, 32) * 2048 : 256;
                 for (int i = 0; i < t; ++i) {
                     SBX0[dir][i] = b.take(sbytes);
                     Wp[dir][i] = b.take(a1);
@@ -191,11 +202,11 @@ struct Plan {
         // buffer each, recomputed from Pt[i] at the top of the frame's reconstruction backward (2.4 GB per frame at 540p x4)
         for (int i = 0; i < nrec; ++i) {
             Pt[i] = b.take(a1);
-            if (diet && i > 0) { U0[i] = U0[0]; U1[i] = U1[0]; C0[i] = C0[0]; } else { U0[i] = b.take(a2); U1[i] = ups == 2 ? b.take(a4) : U0[i]; C0[i] = b.take(a4); }
+            if (diet && i > 0) { U0[i] = U0[0]; U1[i] = U1[0]; C0[i] = C0[0]; } else { U0[i] = b.take(a2); U1[i] = ups == 2 ? b.take(a4) : U0[i]; C0[i] = b.take(a4h); }
         }
         for (int i = nrec; i < t; ++i) { Pt[i] = Pt[0]; U0[i] = U0[0]; U1[i] = U1[0]; C0[i] = C0[0]; }
         SBC0.assign(t, 0); SBPt.assign(t, 0);
-        if (bwd && dtype == VSR_BF16)
+        if (sb)
             for (int i = 0; i < t; ++i) {
                 SBC0[i] = b.take((size_t)n * cdiv(scale * h, 8) * cdiv(scale * w, 32) * 2048);
                 SBPt[i] = b.take((size_t)n * cdiv(h, 8) * cdiv(w, 32) * 2048);
@@ -224,12 +235,12 @@ struct Plan {
             for (int i = 0; i < t; ++i) { dFeatB[i] = b.take(a1); dFF[i] = b.take(a1); }
             for (int dir = 0; dir < 2; ++dir) { S[dir] = b.take(s_elems * 8); dWp[dir] = b.take(a1); }
             far_cnt = b.take((size_t)2 * 32 * 4);
-            G_C0 = b.take(a4); G_P = b.take(a1);
+            G_C0 = b.take(a4h); G_P = b.take(a1);
             // diet: dU1 is written after C0's last use and dU0 after U1's (recon_backward): they take those buffers
             // (upscale 2: there is no U1 / dU1; dU0 is conv_last.0's data gradient and takes C0's buffer in the diet arena)
             // r04 (full arena, bf16, persistent kernels): both are stored as four phase planes, whose 32-pixel row padding can exceed the
             // whole image's (2 ceil(x) >= ceil(2 x)): four planes of the next lower resolution each
-            unsh = !diet && dtype == VSR_BF16 && !vsr_env().generic_conv;
+            unsh = !diet && dtype == VSR_BF16 && !vsr_env().generic_conv && C == 64;
             const size_t gu1 = unsh && 4 * a2 > a4 ? 4 * a2 : a4, gu0 = unsh && 4 * a1 > a2 ? 4 * a1 : a2;
             if (ups == 2) { if (diet) { G_U1 = C0[0]; G_U0 = U1[0]; } else { G_U1 = b.take(gu1); G_U0 = b.take(gu0); } }
             else { G_U0 = diet ? C0[0] : b.take(gu0); G_U1 = G_U0; }
@@ -246,7 +257,7 @@ struct Plan {
             for (int k = 0; k < 2; ++k) slab[k] = b.take((size_t)VSR_WGRAD_NWG * stride * 4);
         }
         // the trunk chains' work / row counters (conv3x3_chain.hip), one block per direction (= per stream)
-        for (int dir = 0; dir < 2; ++dir) chain_sync[dir] = (bwd && dtype == VSR_BF16) ? b.take(vsr_chain_sync_bytes(VSR_CHAIN_MAX_LAYERS, n, h, w)) : 0;
+        for (int dir = 0; dir < 2; ++dir) chain_sync[dir] = sb ? b.take(vsr_chain_sync_bytes(VSR_CHAIN_MAX_LAYERS, n, h, w)) : 0;
         // appended last, so that every other offset is the same in modes 1 and 2
         dflows = 0;
         if (flowgrad && t > 1) {
@@ -274,6 +285,7 @@ struct Ctx {
     const float* fat(size_t off) const { return reinterpret_cast<const float*>(ws + off); }
 
     ConvArgs base(int N, int H, int W) const {
+        const int C = p.C;
         ConvArgs a = {};
         a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1;
         a.out_step = 1; a.Hd = H; a.Wd = W; a.CD = C; a.cout_real = C; a.dst_nstride = pm_image_elems(H, W, C);
@@ -285,26 +297,28 @@ struct Ctx {
     static void set_unshuffle(ConvArgs& a, int N, int H, int W) {
         a.unshuffle = 1; a.unshuffle_plane = plane_elems(N, H, W); a.dst_nstride = pm_image_elems(H / 2, W / 2, C);
     }
-    // y = act(conv3x3(x) + bias) (+res) (*mask(aux)) -- 64 -> 64 at one resolution
+    // y = act(conv3x3(x) + bias) (+res) (*mask(aux)) -- C -> C at one resolution (C = p.C; sign bits at C = 64 only)
     int conv64(const void* x, size_t wpack, const float* bias, void* y, int act, const void* res, const void* aux, int mask,
                int N, int H, int W, void* sign_out = nullptr, const void* sign_bits = nullptr, bool unshuffle = false) const {
         ConvArgs a = base(N, H, W);
         a.src[0] = x; a.wpack = at(wpack); a.bias = bias; a.dst[0] = y; a.act = act; a.res[0] = res; a.aux[0] = aux; a.mask_mode = mask;
         a.sign_out[0] = sign_out; a.sign_bits[0] = sign_bits;
         if (unshuffle) set_unshuffle(a, N, H, W);
+        if (p.C != 64) return vsr_launch_conv(dtype, 3, 1, p.C, p.C, 0, p.CO, EPI_NHWC, a, st);
         const int rc = vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
         // VSRLAB_AMD_GENERIC_CONV=1 (A/B switch): the generic kernel does not write sign bits, but later launches (hr_tail.hip's
         // conv_last.2 data gradient, the masked data gradients) read them -- r04: the switch gave wrong gradients since round 2
         if (rc == VSR_OK && sign_out && dtype == VSR_BF16 && vsr_env().generic_conv) return vsr_launch_sign_bits_c64(y, sign_out, N, H, W, st);
         return rc;
     }
-    // conv3x3 64->256 + PixelShuffle(2): x (N,H,W,64) -> y (N,2H,2W,64)   (upsampling.py:10-12)
+    // conv3x3 C->4C + PixelShuffle(2): x (N,H,W,C) -> y (N,2H,2W,C)   (upsampling.py:10-12)
     int conv_ps(const void* x, size_t wpack, const float* bias4, void* y, int N, int H, int W) const {
+        const int C = p.C;
         ConvArgs a = base(N, H, W);
-        a.src[0] = x; a.wpack = at(wpack); a.w_zstride = 9 * C * C; a.bias = bias4; a.bias_zstride = C; a.nz = 4;
+        a.src[0] = x; a.wpack = at(wpack); a.w_zstride = 9 * p.CO * C; a.bias = bias4; a.bias_zstride = C; a.nz = 4;
         a.out_step = 2; a.Hd = 2 * H; a.Wd = 2 * W; a.dst_nstride = pm_image_elems(2 * H, 2 * W, C);
         for (int z = 0; z < 4; ++z) { a.dst[z] = y; a.out_oy[z] = z >> 1; a.out_ox[z] = z & 1; }
-        return vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+        return vsr_launch_conv(dtype, 3, 1, C, C, 0, p.CO, EPI_NHWC, a, st);
     }
     // data gradient of the above: dy (N,2H,2W,64) -> dx (N,H,W,64) (* mask(aux)) = sum over the 4 pixel-shuffle
     // phases z of a transposed 3x3 64->64 conv of dy's phase z.  bf16: four launches of the persistent kernel (the
@@ -314,9 +328,11 @@ struct Ctx {
     // dy_planes: dy is stored phase-separated (four N x H x W planes, written by a launch with ConvArgs::unshuffle): phase z is then a
     // contiguous tensor instead of every second pixel of every second row of the 2H x 2W image (r04: the strided form fetched every
     // line of dy twice per data gradient and again twice per weight gradient); dx_planes: write dx phase-separated in turn.
+    // C < 64: the one 4-source launch in both dtypes (the persistent kernel is 64-channel).
     int conv_ps_dgrad(const void* dy, size_t wpackd, void* dx, const void* aux, int mask, int N, int H, int W, const void* sign_bits = nullptr,
                       bool dy_planes = false, bool dx_planes = false) const {
-        if (dtype == VSR_BF16) {
+        const int C = p.C;
+        if (dtype == VSR_BF16 && C == 64) {
             for (int z = 0; z < 4; ++z) {
                 ConvArgs a = base(N, H, W);
                 if (dy_planes) {
@@ -338,7 +354,7 @@ struct Ctx {
         a.nz = 1; a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
         for (int s = 0; s < 4; ++s) { a.src[s] = dy; a.src_oy[s] = s >> 1; a.src_ox[s] = s & 1; a.src_nstride[s] = pm_image_elems(2 * H, 2 * W, C); }
         a.wpack = at(wpackd); a.dst[0] = dx; a.aux[0] = aux; a.mask_mode = mask;
-        return vsr_launch_conv(dtype, 3, 4, 64, 64, 0, 64, EPI_NHWC, a, st);
+        return vsr_launch_conv(dtype, 3, 4, C, C, 0, p.CO, EPI_NHWC, a, st);
     }
     int pack(const float* w, size_t dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
              int o_add, int mode) const {
@@ -459,37 +475,39 @@ int pack_all(const Ctx& c, const Plan& p, const float* const* prm) {
 int pack_all_collect(const Ctx& c, const Plan& p, const float* const* prm) {
     const PIdx ix{p.rb, p.ups};
     const int dt = c.dtype; (void)dt;
+    const int C = p.C, CO = p.CO;           // (CO: packed rows of a C-output weight set)
     for (int dir = 0; dir < 2; ++dir) {
         const float* sw = prm[ix.stem_w(dir)];
-        // cat([lr_i(3), feat(64)]) (basicvsr.py:56,71): source 0 = feat = input channels 3..66, source 1 = LR = 0..2
-        CK(c.pack(sw, p.stem_w[dir], 9, C, C, C, C, C + 3, 3, 1, 0, 0));
-        CK(c.pack(sw, p.stem_w[dir] + (size_t)9 * C * C * p.es, 9, C, 16, C, 3, C + 3, 0, 1, 0, 0));
+        // cat([lr_i(3), feat(C)]) (basicvsr.py:56,71): source 0 = feat = input channels 3..C+2, source 1 = LR = 0..2
+        CK(c.pack(sw, p.stem_w[dir], 9, CO, C, C, C, C + 3, 3, 1, 0, 0));
+        CK(c.pack(sw, p.stem_w[dir] + (size_t)9 * CO * C * p.es, 9, CO, 16, C, 3, C + 3, 0, 1, 0, 0));
         CK(c.pack_bias(prm[ix.stem_b(dir)], p.stem_b[dir], C));
-        if (p.bwd) CK(c.pack(sw, p.stem_wd[dir], 9, C, C, C, C, C + 3, 3, 1, 0, 1));
+        if (p.bwd) CK(c.pack(sw, p.stem_wd[dir], 9, CO, C, C, C, C + 3, 3, 1, 0, 1));
         if (p.flowgrad) CK(c.pack(sw, p.stem_wd_lr[dir], 9, 32, C, 3, C, C + 3, 0, 1, 0, 1));
         for (int k = 0; k < 2 * p.rb; ++k) {
-            CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_w[dir][k], 9, C, C, C, C, C, 0, 1, 0, 0));
-            if (p.bwd) CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_wd[dir][k], 9, C, C, C, C, C, 0, 1, 0, 1));
+            CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_w[dir][k], 9, CO, C, C, C, C, 0, 1, 0, 0));
+            if (p.bwd) CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_wd[dir][k], 9, CO, C, C, C, C, 0, 1, 0, 1));
             CK(c.pack_bias(prm[ix.blk_b(dir, k)], p.blk_b[dir][k], C));
         }
     }
     for (int s = 0; s < 2; ++s) {
-        CK(c.pack(prm[ix.point_w()], p.point_w + (size_t)s * C * C * p.es, 1, C, C, C, C, 2 * C, s * C, 1, 0, 0));
-        if (p.bwd) CK(c.pack(prm[ix.point_w()], p.point_wd + (size_t)s * C * C * p.es, 1, C, C, C, C, 2 * C, s * C, 1, 0, 1));
+        CK(c.pack(prm[ix.point_w()], p.point_w + (size_t)s * CO * C * p.es, 1, CO, C, C, C, 2 * C, s * C, 1, 0, 0));
+        if (p.bwd) CK(c.pack(prm[ix.point_w()], p.point_wd + (size_t)s * CO * C * p.es, 1, CO, C, C, C, 2 * C, s * C, 1, 0, 1));
     }
     CK(c.pack_bias(prm[ix.point_b()], p.point_b, C));
     for (int k = 0; k < p.ups; ++k)
         for (int z = 0; z < 4; ++z) {
             // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c+2i+j, y, x]  => sub-conv z uses rows 4c+z
-            CK(c.pack(prm[ix.up_w(k)], p.up_w[k] + (size_t)z * 9 * C * C * p.es, 9, C, C, C, C, C, 0, 4, z, 0));
-            if (p.bwd) CK(c.pack(prm[ix.up_w(k)], p.up_wd[k] + (size_t)z * 9 * C * C * p.es, 9, C, C, C, C, C, 0, 4, z, 1));
+            CK(c.pack(prm[ix.up_w(k)], p.up_w[k] + (size_t)z * 9 * CO * C * p.es, 9, CO, C, C, C, C, 0, 4, z, 0));
+            if (p.bwd) CK(c.pack(prm[ix.up_w(k)], p.up_wd[k] + (size_t)z * 9 * CO * C * p.es, 9, CO, C, C, C, C, 0, 4, z, 1));
             CK(c.pack_bias(prm[ix.up_b(k)], p.up_b[k] + (size_t)z * C * 4, C, 4, z));
         }
-    CK(c.pack(prm[ix.last0_w()], p.last0_w, 9, C, C, C, C, C, 0, 1, 0, 0));
-    if (p.bwd) CK(c.pack(prm[ix.last0_w()], p.last0_wd, 9, C, C, C, C, C, 0, 1, 0, 1));
-    CK(c.pack_bias(prm[ix.last0_b()], p.last0_b, C));
-    CK(c.pack(prm[ix.last2_w()], p.last2_w, 9, 32, C, 3, C, C, 0, 1, 0, 0));
-    if (p.bwd) CK(c.pack(prm[ix.last2_w()], p.last2_wd, 9, C, 16, C, 3, C, 0, 1, 0, 1));
+    // conv_last.0: C -> 64 (basicvsr.py:20); its data gradient 64 -> C
+    CK(c.pack(prm[ix.last0_w()], p.last0_w, 9, 64, C, 64, C, C, 0, 1, 0, 0));
+    if (p.bwd) CK(c.pack(prm[ix.last0_w()], p.last0_wd, 9, CO, 64, C, 64, C, 0, 1, 0, 1));
+    CK(c.pack_bias(prm[ix.last0_b()], p.last0_b, 64));
+    CK(c.pack(prm[ix.last2_w()], p.last2_w, 9, 32, 64, 3, 64, 64, 0, 1, 0, 0));
+    if (p.bwd) CK(c.pack(prm[ix.last2_w()], p.last2_wd, 9, 64, 16, 64, 3, 64, 0, 1, 0, 1));
     CK(c.pack_bias(prm[ix.last2_b()], p.last2_b, 3));
     if (p.t > 1) CK(spynet_pack(c, p.spy, prm, ix.spy_base()));
     return VSR_OK;
@@ -569,20 +587,31 @@ int trunk_forward(const Ctx& c, const Plan& p, int dir, int i, const void* warpe
         a.src[0] = warped;                                   // null => zeros (first frame of the direction)
         a.src[1] = lrs + (size_t)i * 3 * h * w; a.src_nstride[1] = (long long)p.t * 3 * h * w;
         a.wpack = c.at(p.stem_w[dir]); a.bias = c.fat(p.stem_b[dir]); a.dst[0] = x; a.act = ACT_LEAKY;
-        CK(vsr_launch_conv(c.dtype, 3, 2, 64, 16, 1, 64, EPI_NHWC, a, c.st));
+        CK(vsr_launch_conv(c.dtype, 3, 2, p.C, 16, 1, p.CO, EPI_NHWC, a, c.st));
         // the stem runs on the generic two-source kernel: its LeakyReLU sign bits for the block-0 data gradient come from a 66 MB pass
-        if (p.bwd && c.dtype == VSR_BF16) CK(vsr_launch_sign_bits_c64(x, c.at(p.SBX0[dir][i]), n, h, w, c.st));
+        if (p.sb) CK(vsr_launch_sign_bits_c64(x, c.at(p.SBX0[dir][i]), n, h, w, c.st));
     }
     if (chain_on(p)) return trunk_chain_forward(c, p, dir, i);
     for (int b = 0; b < rb; ++b) {      // x + conv2(relu(conv1(x)))   (conv.py:89-92)
         void* act = p.bwd ? c.at(p.aoff(dir, i, b)) : c.at(p.scratchA[dir]);
         void* xn = p.bwd ? c.at(p.xoff(dir, i, b + 1)) : x;   // inference: in place (residual read = own pixel)
         CK(c.conv64(x, p.blk_w[dir][2 * b], c.fat(p.blk_b[dir][2 * b]), act, ACT_RELU, nullptr, nullptr, 0, n, h, w,
-                    (p.bwd && c.dtype == VSR_BF16) ? c.at(p.sboff(dir, i, b)) : nullptr));
+                    p.sb ? c.at(p.sboff(dir, i, b)) : nullptr));
         CK(c.conv64(act, p.blk_w[dir][2 * b + 1], c.fat(p.blk_b[dir][2 * b + 1]), xn, ACT_NONE, x, nullptr, 0, n, h, w));
         x = xn;
     }
     return VSR_OK;
+}
+
+// conv_last.0 + LeakyReLU (basicvsr.py:20-21): U1[i] (C channels) -> C0[i] (64 channels) at the output size
+int last0_forward(const Ctx& c, const Plan& p, int i, void* sign_out) {
+    const int S = p.scale;
+    if (p.C == 64)
+        return c.conv64(c.at(p.U1[i]), p.last0_w, c.fat(p.last0_b), c.at(p.C0[i]), ACT_LEAKY, nullptr, nullptr, 0, p.n, S * p.h, S * p.w, sign_out);
+    ConvArgs a = c.base(p.n, S * p.h, S * p.w);
+    a.src[0] = c.at(p.U1[i]); a.wpack = c.at(p.last0_w); a.bias = c.fat(p.last0_b); a.dst[0] = c.at(p.C0[i]); a.act = ACT_LEAKY;
+    a.CD = 64; a.cout_real = 64; a.dst_nstride = pm_image_elems(S * p.h, S * p.w, 64);
+    return vsr_launch_conv(c.dtype, 3, 1, p.C, p.C, 0, 64, EPI_NHWC, a, c.st);
 }
 
 int recon_forward(const Ctx& c, const Plan& p, int i, const float* lrs, float* sr) {
@@ -591,16 +620,16 @@ int recon_forward(const Ctx& c, const Plan& p, int i, const float* lrs, float* s
         ConvArgs a = c.base(n, h, w);       // point_conv on cat([outputs[i], feat_prop]) (basicvsr.py:75-77)
         a.src[0] = c.at(p.feat[0][i]); a.src[1] = c.at(p.feat[1][i]);
         a.wpack = c.at(p.point_w); a.bias = c.fat(p.point_b); a.dst[0] = c.at(p.Pt[i]); a.act = ACT_LEAKY;
-        CK(vsr_launch_conv(c.dtype, 1, 2, 64, 64, 0, 64, EPI_NHWC, a, c.st));
-        if (p.bwd && c.dtype == VSR_BF16) CK(vsr_launch_sign_bits_c64(c.at(p.Pt[i]), c.at(p.SBPt[i]), n, h, w, c.st));   // mask of upsample.0's data gradient
+        CK(vsr_launch_conv(c.dtype, 1, 2, p.C, p.C, 0, p.CO, EPI_NHWC, a, c.st));
+        if (p.sb) CK(vsr_launch_sign_bits_c64(c.at(p.Pt[i]), c.at(p.SBPt[i]), n, h, w, c.st));   // mask of upsample.0's data gradient
     }
     const int S = p.scale;                     // upscale: S / 2 PixelShufflePacks (basicvsr.py:19); U1 = U0 for S = 2 (Plan::build)
     CK(c.conv_ps(c.at(p.Pt[i]), p.up_w[0], c.fat(p.up_b[0]), c.at(p.U0[i]), n, h, w));
     if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), p.up_w[1], c.fat(p.up_b[1]), c.at(p.U1[i]), n, 2 * h, 2 * w));
-    CK(c.conv64(c.at(p.U1[i]), p.last0_w, c.fat(p.last0_b), c.at(p.C0[i]), ACT_LEAKY, nullptr, nullptr, 0, n, S * h, S * w,
-                (p.bwd && c.dtype == VSR_BF16) ? c.at(p.SBC0[i]) : nullptr));
+    CK(last0_forward(c, p, i, p.sb ? c.at(p.SBC0[i]) : nullptr));
     {
         ConvArgs a = c.base(n, S * h, S * w);   // conv_last.2 + bilinear xS skip (basicvsr.py:21-22,82)
+        a.src_nstride[0] = pm_image_elems(S * h, S * w, 64);
         a.src[0] = c.at(p.C0[i]); a.wpack = c.at(p.last2_w); a.bias = c.fat(p.last2_b); a.cout_real = 3;
         a.dst[0] = sr + (size_t)i * 3 * S * S * h * w; a.dst_nstride = (long long)p.t * 3 * S * S * h * w;
         a.base_lr = lrs + (size_t)i * 3 * h * w; a.base_nstride = (long long)p.t * 3 * h * w; a.base_h = h; a.base_w = w; a.base_scale = S;
@@ -665,7 +694,7 @@ int forward_chain(const Ctx& c, const Plan& p, int dir, const float* lrs) {
         if (k > 0) {
             const int prev = dir == 0 ? i + 1 : i - 1;
             warped = p.bwd ? c.at(p.Wp[dir][i]) : c.at(p.scratchW[dir]);
-            CK(vsr_launch_warp_fwd(c.dtype, c.at(p.feat[dir][prev]), flow_ptr(c, p, dir, dir == 0 ? i : i - 1), warped, n, h, w, C, fstride, c.st));
+            CK(vsr_launch_warp_fwd(c.dtype, c.at(p.feat[dir][prev]), flow_ptr(c, p, dir, dir == 0 ? i : i - 1), warped, n, h, w, p.C, fstride, c.st));
         }
         CK(trunk_forward(c, p, dir, i, warped, lrs));
     }
@@ -720,11 +749,11 @@ struct WG {   // one weight-gradient launch + reduction
     }
 };
 
-WgradArgs wg_base(int N, int H, int W) {
+WgradArgs wg_base(int N, int H, int W, int Cx = C, int Cy = C) {       // Cx / Cy: channels of the pixel-major X / dY
     WgradArgs a = {};
     a.N = N; a.H = H; a.W = W; a.nseg = 1;
-    a.x_step = 1; a.Hx = H; a.Wx = W; a.x_nstride = pm_image_elems(H, W, C);
-    a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, C);
+    a.x_step = 1; a.Hx = H; a.Wx = W; a.x_nstride = pm_image_elems(H, W, Cx);
+    a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, Cy);
     return a;
 }
 
@@ -804,10 +833,11 @@ int recon_ps_wgrads(const Ctx& c, const Plan& p, int k, int f0, int f1, float* c
     const PIdx ix{p.rb, p.ups};
     const WG wg{c};
     const int n = p.n, H = (k + 1) * p.h, W = (k + 1) * p.w;              // the layer's input size: h x w (k = 0), 2h x 2w (k = 1)
+    const int C = p.C;
     for (int i0 = f0; i0 < f1; i0 += VSR_WG_MAXSEG) {
         const int i1 = i0 + VSR_WG_MAXSEG < f1 ? i0 + VSR_WG_MAXSEG : f1;
         for (int z = 0; z < 4; ++z) {
-            WgradArgs a = wg_base(n, H, W);
+            WgradArgs a = wg_base(n, H, W, C, C);
             a.nseg = 0;
             for (int i = i0; i < i1; ++i) {
                 a.x[a.nseg] = c.at(k == 1 ? p.U0[i] : p.Pt[i]);
@@ -816,7 +846,7 @@ int recon_ps_wgrads(const Ctx& c, const Plan& p, int k, int f0, int f1, float* c
                 ++a.nseg;
             }
             if (!p.unsh) { a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C); }
-            CK(wg.run(3, 64, false, 64, false, a, C, C, g[ix.up_w(k)], C, 0, 4, z, g[ix.up_b(k)]));
+            CK(wg.run(3, C, false, C, false, a, C, C, g[ix.up_w(k)], C, 0, 4, z, g[ix.up_b(k)]));
         }
     }
     return VSR_OK;
@@ -825,13 +855,14 @@ int recon_ps_wgrads(const Ctx& c, const Plan& p, int k, int f0, int f1, float* c
 int recon_point_wgrads(const Ctx& c, const Plan& p, int f0, int f1, float* const* g) {
     const PIdx ix{p.rb, p.ups};
     const WG wg{c};
+    const int C = p.C;
     for (int i0 = f0; i0 < f1; i0 += VSR_WG_MAXSEG) {
         const int i1 = i0 + VSR_WG_MAXSEG < f1 ? i0 + VSR_WG_MAXSEG : f1;
         for (int s = 0; s < 2; ++s) {
-            WgradArgs a = wg_base(p.n, p.h, p.w);
+            WgradArgs a = wg_base(p.n, p.h, p.w, C, C);
             a.nseg = 0;
             for (int i = i0; i < i1; ++i) { a.x[a.nseg] = c.at(p.feat[s][i]); a.dy[a.nseg] = c.at(p.GPf[i]); ++a.nseg; }
-            CK(wg.run(1, 64, false, 64, false, a, C, C, g[ix.point_w()], 2 * C, s * C, 1, 0, s == 0 ? g[ix.point_b()] : nullptr));
+            CK(wg.run(1, C, false, C, false, a, C, C, g[ix.point_w()], 2 * C, s * C, 1, 0, s == 0 ? g[ix.point_b()] : nullptr));
         }
     }
     return VSR_OK;
@@ -843,31 +874,39 @@ int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const f
     if (p.diet) {   // U0, U1 and C0 of this frame were not kept: the forward's three launches again (the sign bits of C0 were)
         CK(c.conv_ps(c.at(p.Pt[i]), p.up_w[0], c.fat(p.up_b[0]), c.at(p.U0[i]), p.n, p.h, p.w));
         if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), p.up_w[1], c.fat(p.up_b[1]), c.at(p.U1[i]), p.n, 2 * p.h, 2 * p.w));
-        CK(c.conv64(c.at(p.U1[i]), p.last0_w, c.fat(p.last0_b), c.at(p.C0[i]), ACT_LEAKY, nullptr, nullptr, 0, p.n, p.scale * p.h, p.scale * p.w, nullptr));
+        CK(last0_forward(c, p, i, nullptr));
     }
+    const int C = p.C;
     const int n = p.n, h = p.h, w = p.w, H4 = p.scale * h, W4 = p.scale * w;      // (the output size: 4h x 4w, or 2h x 2w for upscale 2)
     const float* dsr_i = dsr + (size_t)i * 3 * H4 * W4;
     const long long dsr_ns = (long long)p.t * 3 * H4 * W4;
     if (c.dtype == VSR_BF16 && last2_w) {   // d(conv_last.0 pre-activation) = dgrad(conv_last.2)(dsr) * LeakyReLU'(C0): hr_tail.hip
-        CK(vsr_launch_last2_dgrad(dsr_i, dsr_ns, last2_w, c.at(p.C0[i]), c.at(p.G_C0), n, H4, W4, MASK_LEAKY, c.st, c.at(p.SBC0[i])));
+        CK(vsr_launch_last2_dgrad(dsr_i, dsr_ns, last2_w, c.at(p.C0[i]), c.at(p.G_C0), n, H4, W4, MASK_LEAKY, c.st, p.sb ? c.at(p.SBC0[i]) : nullptr));
     } else {
         ConvArgs a = c.base(n, H4, W4);
         a.src[0] = dsr_i; a.src_nstride[0] = dsr_ns; a.wpack = c.at(p.last2_wd); a.dst[0] = c.at(p.G_C0);
         a.aux[0] = c.at(p.C0[i]); a.mask_mode = MASK_LEAKY;
+        a.CD = 64; a.cout_real = 64; a.dst_nstride = pm_image_elems(H4, W4, 64);
         CK(vsr_launch_conv(c.dtype, 3, 1, 16, 16, 1, 64, EPI_NHWC, a, c.st));
     }
     {   // conv_last.2: X = C0, dY = dsr (planar)
-        WgradArgs a = wg_base(n, H4, W4);
+        WgradArgs a = wg_base(n, H4, W4, 64, 64);
         a.x[0] = c.at(p.C0[i]); a.dy[0] = dsr_i; a.dy_nstride = dsr_ns;
-        CK(wg.run(3, 64, false, 16, true, a, 3, C, g[ix.last2_w()], C, 0, 1, 0, g[ix.last2_b()]));
+        CK(wg.run(3, 64, false, 16, true, a, 3, 64, g[ix.last2_w()], 64, 0, 1, 0, g[ix.last2_b()]));
     }
     // (r04: G_U1 / G_U0, the gradients into the pixel-shuffle layers, are written phase-separated when p.unsh)
     const size_t gu1 = p.GU1f[i], gu0 = p.GU0f[i], gp = p.GPf[i];     // (per frame when p.hrdef: their weight gradients run later, all frames per launch)
-    CK(c.conv64(c.at(p.G_C0), p.last0_wd, nullptr, c.at(gu1), ACT_NONE, nullptr, nullptr, 0, n, H4, W4, nullptr, nullptr, p.unsh));
+    if (C == 64) {
+        CK(c.conv64(c.at(p.G_C0), p.last0_wd, nullptr, c.at(gu1), ACT_NONE, nullptr, nullptr, 0, n, H4, W4, nullptr, nullptr, p.unsh));
+    } else {    // conv_last.0's data gradient 64 -> C
+        ConvArgs a = c.base(n, H4, W4);
+        a.src[0] = c.at(p.G_C0); a.src_nstride[0] = pm_image_elems(H4, W4, 64); a.wpack = c.at(p.last0_wd); a.dst[0] = c.at(gu1);
+        CK(vsr_launch_conv(c.dtype, 3, 1, 64, 64, 0, p.CO, EPI_NHWC, a, c.st));
+    }
     {   // conv_last.0: X = U1, dY = G_C0
-        WgradArgs a = wg_base(n, H4, W4);
+        WgradArgs a = wg_base(n, H4, W4, C, 64);
         a.x[0] = c.at(p.U1[i]); a.dy[0] = c.at(p.G_C0);
-        CK(wg.run(3, 64, false, 64, false, a, C, C, g[ix.last0_w()], C, 0, 1, 0, g[ix.last0_b()]));
+        CK(wg.run(3, C, false, 64, false, a, 64, C, g[ix.last0_w()], C, 0, 1, 0, g[ix.last0_b()]));
     }
     // upsample.1 (at 2h x 2w; upscale 4 only -- for upscale 2 G_U1 IS G_U0): dgrad, then wgrad per pixel-shuffle phase z
     if (p.ups == 2) {
@@ -875,13 +914,13 @@ int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const f
         if (!p.hrdef) CK(recon_ps_wgrads(c, p, 1, i, i + 1, g));
     }
     // upsample.0 (at h x w): its input is LeakyReLU(point_conv) => mask with P
-    CK(c.conv_ps_dgrad(c.at(gu0), p.up_wd[0], c.at(gp), c.at(p.Pt[i]), MASK_LEAKY, n, h, w, c.dtype == VSR_BF16 ? c.at(p.SBPt[i]) : nullptr, p.unsh, false));
+    CK(c.conv_ps_dgrad(c.at(gu0), p.up_wd[0], c.at(gp), c.at(p.Pt[i]), MASK_LEAKY, n, h, w, p.sb ? c.at(p.SBPt[i]) : nullptr, p.unsh, false));
     if (!p.hrdef) CK(recon_ps_wgrads(c, p, 0, i, i + 1, g));
     {   // point_conv dgrad: two 64-channel outputs (d outputs[i], d feat_prop)
         ConvArgs a = c.base(n, h, w);
-        a.src[0] = c.at(gp); a.wpack = c.at(p.point_wd); a.w_zstride = C * C; a.nz = 2;
+        a.src[0] = c.at(gp); a.wpack = c.at(p.point_wd); a.w_zstride = p.CO * C; a.nz = 2;
         a.dst[0] = c.at(p.dFeatB[i]); a.dst[1] = c.at(p.dFF[i]);
-        CK(vsr_launch_conv(c.dtype, 1, 1, 64, 64, 0, 64, EPI_NHWC, a, c.st));
+        CK(vsr_launch_conv(c.dtype, 1, 1, C, C, 0, p.CO, EPI_NHWC, a, c.st));
     }
     if (!p.hrdef) CK(recon_point_wgrads(c, p, i, i + 1, g));
     return VSR_OK;
@@ -900,9 +939,9 @@ int trunk_backward(const Ctx& c, const Plan& p, int dir, int i, const void* dtop
     if (pending_flow) {
         const long long fstride = (long long)(p.t - 1) * 2 * h * w;
         CK(vsr_launch_warp_bwd_gather(c.dtype, c.at(p.dWp[dir]), pending_flow, dtop, (long long*)c.at(p.S[dir]),
-                                      (int*)c.at(p.far_cnt) + dir * 32 + pending_k, c.at(p.dxoff(dir, i, rb)), n, h, w, fstride, c.st));
+                                      (int*)c.at(p.far_cnt) + dir * 32 + pending_k, c.at(p.dxoff(dir, i, rb)), n, h, w, p.C, fstride, c.st));
     } else {
-        CK(vsr_launch_add_cast(c.dtype, dtop, nullptr, c.at(p.dxoff(dir, i, rb)), n, h, w, C, c.st));
+        CK(vsr_launch_add_cast(c.dtype, dtop, nullptr, c.at(p.dxoff(dir, i, rb)), n, h, w, p.C, c.st));
     }
     const bool chain = chain_on(p) && !p.diet;            // diet: the activation gradients live in a two-block ring, the frame's weight
     if (chain) CK(trunk_chain_backward(c, p, dir, i));     // gradients are launched block by block behind them (the forward chain stays)
@@ -910,11 +949,11 @@ int trunk_backward(const Ctx& c, const Plan& p, int dir, int i, const void* dtop
         const void* dxn = c.at(p.dxoff(dir, i, b + 1));
         // dA = dgrad(conv2)(dX_{b+1}) * ReLU'(A_b)
         if (!chain) CK(c.conv64(dxn, p.blk_wd[dir][2 * b + 1], nullptr, c.at(p.g1off(dir, i, b)), ACT_NONE, nullptr, c.at(p.aoff(dir, i, b)), MASK_RELU, n, h, w,
-                    nullptr, c.dtype == VSR_BF16 ? c.at(p.sboff(dir, i, b)) : nullptr));
+                    nullptr, p.sb ? c.at(p.sboff(dir, i, b)) : nullptr));
         // dX_b = dX_{b+1} + dgrad(conv1)(dA); for b == 0 also through the stem's LeakyReLU
         void* out = b > 0 ? c.at(p.dxoff(dir, i, b)) : c.at(p.G0[dir][i]);
         CK(c.conv64(c.at(p.g1off(dir, i, b)), p.blk_wd[dir][2 * b], nullptr, out, ACT_NONE, dxn, b == 0 ? c.at(p.xoff(dir, i, 0)) : nullptr,
-                    b == 0 ? MASK_LEAKY : 0, n, h, w, nullptr, (b == 0 && c.dtype == VSR_BF16) ? c.at(p.SBX0[dir][i]) : nullptr));
+                    b == 0 ? MASK_LEAKY : 0, n, h, w, nullptr, (b == 0 && p.sb) ? c.at(p.SBX0[dir][i]) : nullptr));
         if (p.diet) CK(block_wgrads(c, p, dir, b, i, i + 1, g));
     }
     if (has_warp)   // gradient w.r.t. the warped state (feat part of the stem's input)
@@ -927,22 +966,22 @@ int trunk_backward(const Ctx& c, const Plan& p, int dir, int i, const void* dtop
 int stem_wgrads(const Ctx& c, const Plan& p, int dir, int f0, int f1, const float* lrs, float* const* g) {
     const PIdx ix{p.rb, p.ups};
     const WG wg{c};
-    const int n = p.n, t = p.t, h = p.h, w = p.w;
+    const int n = p.n, t = p.t, h = p.h, w = p.w, C = p.C;
     {   // LR part (+ bias)
-        WgradArgs a = wg_base(n, h, w);
+        WgradArgs a = wg_base(n, h, w, C, C);
         a.nseg = 0;
         for (int i = f0; i < f1; ++i) { a.x[a.nseg] = lrs + (size_t)i * 3 * h * w; a.dy[a.nseg] = c.at(p.G0[dir][i]); ++a.nseg; }
         a.x_nstride = (long long)t * 3 * h * w;
-        CK(wg.run(3, 16, true, 64, false, a, C, 3, g[ix.stem_w(dir)], C + 3, 0, 1, 0, g[ix.stem_b(dir)]));
+        CK(wg.run(3, 16, true, C, false, a, C, 3, g[ix.stem_w(dir)], C + 3, 0, 1, 0, g[ix.stem_b(dir)]));
     }
     {   // feat part: only frames that had a warped state
-        WgradArgs a = wg_base(n, h, w);
+        WgradArgs a = wg_base(n, h, w, C, C);
         a.nseg = 0;
         for (int i = f0; i < f1; ++i) {
             const bool has = dir == 0 ? (i < t - 1) : (i > 0);
             if (has) { a.x[a.nseg] = c.at(p.Wp[dir][i]); a.dy[a.nseg] = c.at(p.G0[dir][i]); ++a.nseg; }
         }
-        if (a.nseg) CK(wg.run(3, 64, false, 64, false, a, C, C, g[ix.stem_w(dir)], C + 3, 3, 1, 0, nullptr));
+        if (a.nseg) CK(wg.run(3, C, false, C, false, a, C, C, g[ix.stem_w(dir)], C + 3, 3, 1, 0, nullptr));
     }
     return VSR_OK;
 }
@@ -950,14 +989,15 @@ int stem_wgrads(const Ctx& c, const Plan& p, int dir, int f0, int f1, const floa
 int block_wgrads(const Ctx& c, const Plan& p, int dir, int b, int f0, int f1, float* const* g) {
     const PIdx ix{p.rb, p.ups};
     const WG wg{c};
-    WgradArgs a1 = wg_base(p.n, p.h, p.w), a2 = wg_base(p.n, p.h, p.w);
+    const int C = p.C;
+    WgradArgs a1 = wg_base(p.n, p.h, p.w, C, C), a2 = wg_base(p.n, p.h, p.w, C, C);
     a1.nseg = a2.nseg = 0;
     for (int i = f0; i < f1; ++i) {
         a1.x[a1.nseg] = c.at(p.xoff(dir, i, b)); a1.dy[a1.nseg] = c.at(p.g1off(dir, i, b)); ++a1.nseg;
         a2.x[a2.nseg] = c.at(p.aoff(dir, i, b)); a2.dy[a2.nseg] = c.at(p.dxoff(dir, i, b + 1)); ++a2.nseg;
     }
-    CK(wg.run(3, 64, false, 64, false, a1, C, C, g[ix.blk_w(dir, 2 * b)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b)]));
-    CK(wg.run(3, 64, false, 64, false, a2, C, C, g[ix.blk_w(dir, 2 * b + 1)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b + 1)]));
+    CK(wg.run(3, C, false, C, false, a1, C, C, g[ix.blk_w(dir, 2 * b)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b)]));
+    CK(wg.run(3, C, false, C, false, a2, C, C, g[ix.blk_w(dir, 2 * b + 1)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b + 1)]));
     return VSR_OK;
 }
 int trunk_wgrads(const Ctx& c, const Plan& p, int dir, const float* lrs, float* const* g) {
@@ -989,7 +1029,7 @@ int backward_chain(const Ctx& c, const Plan& p, int dir, const float* lrs, float
             if (p.flowgrad) {   // the same warp's gradient w.r.t. its flow (each flow is used by exactly one warp)
                 const int prev = dir == 1 ? i - 1 : i + 1, fi = dir == 1 ? i - 1 : i;
                 float* df = (float*)c.at(p.dflows) + ((size_t)dir * p.n * (p.t - 1) + fi) * 2 * p.h * p.w;
-                CK(vsr_launch_warp_bwd_flow(c.dtype, c.at(p.feat[dir][prev]), c.at(p.dWp[dir]), flow_ptr(c, p, dir, fi), df, n, h, w, C, fstride, c.st));
+                CK(vsr_launch_warp_bwd_flow(c.dtype, c.at(p.feat[dir][prev]), c.at(p.dWp[dir]), flow_ptr(c, p, dir, fi), df, n, h, w, p.C, fstride, c.st));
             }
         }
     }
@@ -1022,7 +1062,7 @@ int backward_impl(const Plan& p, const float* const* prm, float* const* g, const
                 a.src[0] = c.at(p.G0[dir][i]); a.wpack = c.at(p.stem_wd_lr[dir]); a.cout_real = 3;
                 float* d = dlrs + (size_t)i * 3 * p.h * p.w;
                 a.dst[0] = d; a.pres = d; a.dst_nstride = (long long)p.t * 3 * p.h * p.w;
-                CK(vsr_launch_conv(c.dtype, 3, 1, 64, 64, 0, 32, EPI_PLANAR, a, c.st));
+                CK(vsr_launch_conv(c.dtype, 3, 1, p.C, p.C, 0, 32, EPI_PLANAR, a, c.st));
             }
     }
     if (p.flowgrad && p.t > 1)   // part 3 (and train_flow): through the flows into SPyNet's parameters / image pyramid
@@ -1053,26 +1093,30 @@ int vsr_basicvsr_num_params(const VsrBasicVSRDesc* d) {
     return PIdx{d->res_blocks, d->upscale == 2 ? 1 : 2}.count();
 }
 
-size_t vsr_basicvsr_workspace_bytes(const VsrBasicVSRDesc* d, int need_backward) {
+}  // extern "C"
+
+// The whole-path entries (mid_channels 64) and the narrow ones (16 / 32) differ only in the widths their Plan accepts.
+namespace {
+size_t basicvsr_workspace_bytes(const VsrBasicVSRDesc* d, int need_backward, bool narrow) {
     if (!d) return 0;
     Plan p;
-    if (p.build(*d, need_backward) != VSR_OK) return 0;
+    if (p.build(*d, need_backward, narrow) != VSR_OK) return 0;
     return p.total;
 }
 
-int vsr_basicvsr_forward(const VsrBasicVSRDesc* d, const float* const* params, int nparams, const float* lrs, float* sr,
-                         void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
+int basicvsr_forward(const VsrBasicVSRDesc* d, const float* const* params, int nparams, const float* lrs, float* sr,
+                     void* workspace, size_t workspace_bytes, int need_backward, void* stream, bool narrow) {
     if (!d || !params || !lrs || !sr || !workspace) return VSR_ERR_BADARG;
     Plan p;
-    CK(p.build(*d, need_backward));
+    CK(p.build(*d, need_backward, narrow));
     if (nparams != PIdx{p.rb, p.ups}.count()) return VSR_ERR_BADARG;
     for (int k = 0; k < nparams; ++k) if (!params[k]) return VSR_ERR_BADARG;
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
     return forward_impl(p, params, lrs, sr, (char*)workspace, (hipStream_t)stream);
 }
 
-int vsr_basicvsr_backward(const VsrBasicVSRDesc* d, const float* const* params, float* const* grads, int nparams,
-                          const float* lrs, const float* dsr, float* dlrs, void* workspace, size_t workspace_bytes, void* stream) {
+int basicvsr_backward(const VsrBasicVSRDesc* d, const float* const* params, float* const* grads, int nparams,
+                      const float* lrs, const float* dsr, float* dlrs, void* workspace, size_t workspace_bytes, void* stream, bool narrow) {
     if (!d || !params || !grads || !lrs || !dsr || !workspace) return VSR_ERR_BADARG;
     if (d->res_blocks < 1) return VSR_ERR_UNSUPPORTED;
     const PIdx ix{d->res_blocks, d->upscale == 2 ? 1 : 2};
@@ -1080,21 +1124,48 @@ int vsr_basicvsr_backward(const VsrBasicVSRDesc* d, const float* const* params, 
     bool flow = dlrs != nullptr;                           // input or SPyNet gradient wanted => the forward ran with need_backward = 2
     for (int k = ix.spy_base(); k < ix.spy_mean(); ++k) flow = flow || grads[k];
     Plan p;
-    CK(p.build(*d, flow ? 2 : 1));
+    CK(p.build(*d, flow ? 2 : 1, narrow));
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
     return backward_impl(p, params, grads, lrs, dsr, dlrs, (char*)workspace, (hipStream_t)stream);
 }
 
-int vsr_basicvsr_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward, float* flow_backward, void* stream) {
+int basicvsr_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward, float* flow_backward, void* stream, bool narrow) {
     if (!d || !workspace) return VSR_ERR_BADARG;
     Plan p;
-    CK(p.build(*d, 0));         // weight/flow offsets do not depend on need_backward
+    CK(p.build(*d, 0, narrow));         // weight/flow offsets do not depend on need_backward
     if (p.t < 2) return VSR_OK;
     const size_t half = (size_t)p.n * (p.t - 1) * 2 * p.h * p.w * 4;
     const char* f = (const char*)workspace + p.flows;
     if (flow_backward) HIP_CHECK_RET(hipMemcpyAsync(flow_backward, f, half, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (flow_forward) HIP_CHECK_RET(hipMemcpyAsync(flow_forward, f + half, half, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return VSR_OK;
+}
+}  // namespace
+
+extern "C" {
+size_t vsr_basicvsr_workspace_bytes(const VsrBasicVSRDesc* d, int need_backward) { return basicvsr_workspace_bytes(d, need_backward, false); }
+int vsr_basicvsr_forward(const VsrBasicVSRDesc* d, const float* const* params, int nparams, const float* lrs, float* sr,
+                         void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
+    return basicvsr_forward(d, params, nparams, lrs, sr, workspace, workspace_bytes, need_backward, stream, false);
+}
+int vsr_basicvsr_backward(const VsrBasicVSRDesc* d, const float* const* params, float* const* grads, int nparams,
+                          const float* lrs, const float* dsr, float* dlrs, void* workspace, size_t workspace_bytes, void* stream) {
+    return basicvsr_backward(d, params, grads, nparams, lrs, dsr, dlrs, workspace, workspace_bytes, stream, false);
+}
+int vsr_basicvsr_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward, float* flow_backward, void* stream) {
+    return basicvsr_get_flows(d, workspace, flow_forward, flow_backward, stream, false);
+}
+size_t vsr_basicvsr_narrow_workspace_bytes(const VsrBasicVSRDesc* d, int need_backward) { return basicvsr_workspace_bytes(d, need_backward, true); }
+int vsr_basicvsr_narrow_forward(const VsrBasicVSRDesc* d, const float* const* params, int nparams, const float* lrs, float* sr,
+                                void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
+    return basicvsr_forward(d, params, nparams, lrs, sr, workspace, workspace_bytes, need_backward, stream, true);
+}
+int vsr_basicvsr_narrow_backward(const VsrBasicVSRDesc* d, const float* const* params, float* const* grads, int nparams,
+                                 const float* lrs, const float* dsr, float* dlrs, void* workspace, size_t workspace_bytes, void* stream) {
+    return basicvsr_backward(d, params, grads, nparams, lrs, dsr, dlrs, workspace, workspace_bytes, stream, true);
+}
+int vsr_basicvsr_narrow_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward, float* flow_backward, void* stream) {
+    return basicvsr_get_flows(d, workspace, flow_forward, flow_backward, stream, true);
 }
 
 // ---- SPyNet alone ---------------------------------------------------------------------------------
@@ -1206,10 +1277,12 @@ struct CleanPlan {
     std::vector<size_t> xs;             // [steps]: planar fp32 input of each step (xs[0] unused: the caller's lr)
     std::vector<size_t> X, A;           // [steps][blocks+1] / [steps][blocks]
 };
-static CleanPlan clean_plan(int F, int h, int w, int blocks, int dtype, int steps, bool save) {
+// C: mid channels (64, or 16 / 32 through vsr_cleaner_narrow_workspace_bytes); CO: packed rows of a C-output weight set
+static CleanPlan clean_plan(int F, int h, int w, int blocks, int dtype, int steps, bool save, int C = 64) {
     CleanPlan p; Bump b;
-    const size_t es = esize(dtype), w64 = (size_t)9 * C * C * es;
-    p.stem_w = b.take((size_t)9 * C * 16 * es); p.stem_b = b.take(C * 4);
+    const int CO = C < 32 ? 32 : C;
+    const size_t es = esize(dtype), w64 = (size_t)9 * CO * C * es;
+    p.stem_w = b.take((size_t)9 * CO * 16 * es); p.stem_b = b.take(C * 4);
     p.blk_w.resize(2 * blocks); p.blk_b.resize(2 * blocks);
     for (int k = 0; k < 2 * blocks; ++k) { p.blk_w[k] = b.take(w64); p.blk_b[k] = b.take(C * 4); }
     p.out_w = b.take((size_t)9 * 32 * C * es); p.out_b = b.take(64 * 4);
@@ -1219,7 +1292,7 @@ static CleanPlan clean_plan(int F, int h, int w, int blocks, int dtype, int step
     p.xa = b.take(x1); p.xb = b.take(x1);
     p.save = save;
     if (save) {                                   // appended: the forward-only offsets do not move
-        p.stem_wd = b.take((size_t)9 * 32 * C * es); p.out_wd = b.take((size_t)9 * C * 16 * es);
+        p.stem_wd = b.take((size_t)9 * 32 * C * es); p.out_wd = b.take((size_t)9 * CO * 16 * es);
         p.blk_wd.resize(2 * blocks);
         for (int k = 0; k < 2 * blocks; ++k) p.blk_wd[k] = b.take(w64);
         int cp, xp, stride;
@@ -1243,31 +1316,39 @@ size_t vsr_cleaner_workspace_bytes(int F, int h, int w, int blocks, int steps, i
     return clean_plan(F, h, w, blocks, dtype, steps, need_backward != 0).total;
 }
 
+size_t vsr_cleaner_narrow_workspace_bytes(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, int need_backward) {
+    if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || (mid_channels != 16 && mid_channels != 32)) return 0;
+    if (dtype != VSR_F32 && dtype != VSR_BF16) return 0;
+    return clean_plan(F, h, w, blocks, dtype, steps, need_backward != 0, mid_channels).total;
+}
+static bool cleaner_width_ok(int mid_channels) { return mid_channels == 64 || mid_channels == 32 || mid_channels == 16; }
+
 int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, const float* const* params,
                         int nparams, const float* lr, float* lq, void* workspace, size_t workspace_bytes, int need_backward,
                         void* stream) {
     if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !params || !lr || !lq || !workspace) return VSR_ERR_BADARG;
-    if (mid_channels != C) return VSR_ERR_UNSUPPORTED;
+    if (!cleaner_width_ok(mid_channels)) return VSR_ERR_UNSUPPORTED;
     if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
     if (nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
     const bool save = need_backward != 0;
-    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, save);
+    const int C = mid_channels, CO = C < 32 ? 32 : C;
+    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, save, C);
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype);
+    Plan dummy; dummy.es = esize(dtype); dummy.C = C; dummy.CO = CO;
     const Ctx c{dummy, (char*)workspace, st, dtype};
-    CK(c.pack(params[0], p.stem_w, 9, C, 16, C, 3, 3, 0, 1, 0, 0));
+    CK(c.pack(params[0], p.stem_w, 9, CO, 16, C, 3, 3, 0, 1, 0, 0));
     CK(c.pack_bias(params[1], p.stem_b, C));
     for (int k = 0; k < 2 * blocks; ++k) {
-        CK(c.pack(params[2 + 2 * k], p.blk_w[k], 9, C, C, C, C, C, 0, 1, 0, 0));
+        CK(c.pack(params[2 + 2 * k], p.blk_w[k], 9, CO, C, C, C, C, 0, 1, 0, 0));
         CK(c.pack_bias(params[3 + 2 * k], p.blk_b[k], C));
-        if (save) CK(c.pack(params[2 + 2 * k], p.blk_wd[k], 9, C, C, C, C, C, 0, 1, 0, 1));
+        if (save) CK(c.pack(params[2 + 2 * k], p.blk_wd[k], 9, CO, C, C, C, C, 0, 1, 0, 1));
     }
     CK(c.pack(params[2 + 4 * blocks], p.out_w, 9, 32, C, 3, C, C, 0, 1, 0, 0));
     CK(c.pack_bias(params[3 + 4 * blocks], p.out_b, 3));
     if (save) {
-        CK(c.pack(params[0], p.stem_wd, 9, 32, C, 3, C, 3, 0, 1, 0, 1));                  // 64 -> 3 (planar epilogue)
-        CK(c.pack(params[2 + 4 * blocks], p.out_wd, 9, C, 16, C, 3, C, 0, 1, 0, 1));      // 3 (planar source) -> 64
+        CK(c.pack(params[0], p.stem_wd, 9, 32, C, 3, C, 3, 0, 1, 0, 1));                  // C -> 3 (planar epilogue)
+        CK(c.pack(params[2 + 4 * blocks], p.out_wd, 9, CO, 16, C, 3, C, 0, 1, 0, 1));     // 3 (planar source) -> C
     }
     const float* xin = lr;
     for (int s = 0; s < steps; ++s) {
@@ -1277,7 +1358,7 @@ int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int s
             ConvArgs a = c.base(F, h, w);
             a.src[0] = xin; a.src_nstride[0] = (long long)3 * h * w;
             a.wpack = c.at(p.stem_w); a.bias = c.fat(p.stem_b); a.dst[0] = Xs(0); a.act = ACT_LEAKY;
-            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, 64, EPI_NHWC, a, st));
+            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st));
         }
         for (int b = 0; b < blocks; ++b) {
             void* act = save ? c.at(p.A[(size_t)s * blocks + b]) : c.at(p.act);
@@ -1288,7 +1369,7 @@ int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int s
             ConvArgs a = c.base(F, h, w);
             a.src[0] = Xs(blocks); a.wpack = c.at(p.out_w); a.bias = c.fat(p.out_b); a.cout_real = 3;
             a.dst[0] = xout; a.dst_nstride = (long long)3 * h * w; a.pres = xin;
-            CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 32, EPI_PLANAR, a, st));
+            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
         }
         xin = xout;
     }
@@ -1301,13 +1382,14 @@ int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int s
 int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, float* const* grads, int nparams,
                          const float* lr, const float* dlq, float* dlr, void* workspace, size_t workspace_bytes, void* stream) {
     if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !grads || !lr || !dlq || !workspace) return VSR_ERR_BADARG;
-    if (mid_channels != C || blocks < 1) return VSR_ERR_UNSUPPORTED;      // the stem's LeakyReLU mask is fused into block 0's dgrad
+    if (!cleaner_width_ok(mid_channels) || blocks < 1) return VSR_ERR_UNSUPPORTED;      // the stem's LeakyReLU mask is fused into block 0's dgrad
     if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
     if (nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
-    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, true);
+    const int C = mid_channels, CO = C < 32 ? 32 : C;
+    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, true, C);
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype); dummy.slab[0] = dummy.slab[1] = p.slab;
+    Plan dummy; dummy.es = esize(dtype); dummy.slab[0] = dummy.slab[1] = p.slab; dummy.C = C; dummy.CO = CO;
     const Ctx c{dummy, (char*)workspace, st, dtype};
     const WG wg{c};
     const float* dx = dlq;                                   // gradient w.r.t. x_{s+1}
@@ -1316,39 +1398,39 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
         auto Xs = [&](int k) { return c.at(p.X[(size_t)s * (blocks + 1) + k]); };
         auto As = [&](int k) { return c.at(p.A[(size_t)s * blocks + k]); };
         float* gow = grads[2 + 4 * blocks]; float* gob = grads[3 + 4 * blocks];
-        {   // out conv 64->3: X = X_blocks, dY = dx (planar)
-            WgradArgs a = wg_base(F, h, w);
+        {   // out conv C->3: X = X_blocks, dY = dx (planar)
+            WgradArgs a = wg_base(F, h, w, C, C);
             a.x[0] = Xs(blocks); a.dy[0] = dx; a.dy_nstride = (long long)3 * h * w;
-            CK(wg.run(3, 64, false, 16, true, a, 3, C, gow, C, 0, 1, 0, gob));
+            CK(wg.run(3, C, false, 16, true, a, 3, C, gow, C, 0, 1, 0, gob));
         }
         size_t dcur = p.dXa, dnext = p.dXb;
         {   // d X_blocks = dgrad(out conv)(dx)
             ConvArgs a = c.base(F, h, w);
             a.src[0] = dx; a.src_nstride[0] = (long long)3 * h * w; a.wpack = c.at(p.out_wd); a.dst[0] = c.at(dcur);
-            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, 64, EPI_NHWC, a, st));
+            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st));
         }
         for (int b = blocks - 1; b >= 0; --b) {   // x + conv2(relu(conv1(x)))   (conv.py:89-92)
             CK(c.conv64(c.at(dcur), p.blk_wd[2 * b + 1], nullptr, c.at(p.dA), ACT_NONE, nullptr, As(b), MASK_RELU, F, h, w));
             {
-                WgradArgs a = wg_base(F, h, w);
+                WgradArgs a = wg_base(F, h, w, C, C);
                 a.x[0] = As(b); a.dy[0] = c.at(dcur);
-                CK(wg.run(3, 64, false, 64, false, a, C, C, grads[2 + 2 * (2 * b + 1)], C, 0, 1, 0, grads[3 + 2 * (2 * b + 1)]));
+                CK(wg.run(3, C, false, C, false, a, C, C, grads[2 + 2 * (2 * b + 1)], C, 0, 1, 0, grads[3 + 2 * (2 * b + 1)]));
             }
             void* out = b > 0 ? c.at(dnext) : c.at(p.G0);      // b == 0: also through the stem's LeakyReLU
             CK(c.conv64(c.at(p.dA), p.blk_wd[2 * b], nullptr, out, ACT_NONE, c.at(dcur), b == 0 ? Xs(0) : nullptr,
                         b == 0 ? MASK_LEAKY : 0, F, h, w));
             {
-                WgradArgs a = wg_base(F, h, w);
+                WgradArgs a = wg_base(F, h, w, C, C);
                 a.x[0] = Xs(b); a.dy[0] = c.at(p.dA);
-                CK(wg.run(3, 64, false, 64, false, a, C, C, grads[2 + 2 * (2 * b)], C, 0, 1, 0, grads[3 + 2 * (2 * b)]));
+                CK(wg.run(3, C, false, C, false, a, C, C, grads[2 + 2 * (2 * b)], C, 0, 1, 0, grads[3 + 2 * (2 * b)]));
             }
             const size_t tmp = dcur; dcur = dnext; dnext = tmp;
         }
         const void* g0 = c.at(p.G0);
-        {   // stem 3->64: X = x_s (planar), dY = G0
-            WgradArgs a = wg_base(F, h, w);
+        {   // stem 3->C: X = x_s (planar), dY = G0
+            WgradArgs a = wg_base(F, h, w, C, C);
             a.x[0] = xs; a.x_nstride = (long long)3 * h * w; a.dy[0] = g0;
-            CK(wg.run(3, 16, true, 64, false, a, C, 3, grads[0], 3, 0, 1, 0, grads[1]));
+            CK(wg.run(3, 16, true, C, false, a, C, 3, grads[0], 3, 0, 1, 0, grads[1]));
         }
         const bool last = s == 0;
         if (!last || dlr) {   // d x_s = d x_{s+1} + dgrad(stem)(G0)
@@ -1356,7 +1438,7 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
             ConvArgs a = c.base(F, h, w);
             a.src[0] = g0; a.wpack = c.at(p.stem_wd); a.cout_real = 3;
             a.dst[0] = dxs; a.dst_nstride = (long long)3 * h * w; a.pres = dx;
-            CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 32, EPI_PLANAR, a, st));
+            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
             dx = dxs;
         }
     }
@@ -1365,6 +1447,7 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
 
 // ---- per-op entry points -------------------------------------------------------------------------
 static bool bad_dtype(int dtype) { return dtype != VSR_F32 && dtype != VSR_BF16; }
+static bool layer_width_ok(int c) { return c == 16 || c == 32 || c == 64; }      // the widths of the per-op trunk / stem / shuffle layers
 static bool bad_dims(int N, int H, int W) { return N < 1 || H < 1 || W < 1; }
 
 int vsr_flow_warp_fwd(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H, int W, int Cc, void* stream) {
@@ -1397,7 +1480,13 @@ int vsr_flow_warp_bwd_ex(int dtype, const void* dout_pm, const float* flow, floa
 extern "C" int vsr_debug_warp_bwd_gather(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
                                          void* out_pm, int N, int H, int W, void* stream) {
     if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, 64, (long long)2 * H * W, (hipStream_t)stream);
+}
+// ... the same at Cc = 16, 32 or 64 channels (S: N*H*W*Cc long longs): the narrow engine's propagation warps
+extern "C" int vsr_debug_warp_bwd_gather_c(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
+                                           void* out_pm, int N, int H, int W, int Cc, void* stream) {
+    if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
+    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
 }
 int vsr_flow_warp_bwd_flow_ex(int dtype, const void* in_pm, const void* dout_pm, const float* flow, float* dflow, int N, int H, int W,
                               int Cc, int padding_mode, void* stream) {
@@ -1413,7 +1502,7 @@ int vsr_pm_to_planar(int dtype, const void* in_pm, float* out, int N, int Cout, 
     return vsr_launch_pm_to_planar(dtype, in_pm, out, N, Cout, H, W, Cc, (hipStream_t)stream);
 }
 
-static ConvArgs plain64(const void* x, const void* wpack, const float* b, void* y, int N, int H, int W) {
+static ConvArgs plain64(const void* x, const void* wpack, const float* b, void* y, int N, int H, int W, int C = 64) {
     ConvArgs a = {};
     a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1; a.out_step = 1; a.Hd = H; a.Wd = W; a.CD = C; a.cout_real = C;
     a.dst_nstride = pm_image_elems(H, W, C); a.src_nstride[0] = pm_image_elems(H, W, C);
@@ -1502,6 +1591,7 @@ int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
         return VSR_ERR_BADARG;
     if (act != ACT_NONE && !(dy_pm ? y_pm != nullptr : y_planar != nullptr)) return VSR_ERR_BADARG;     // the mask needs the layer's output
     if (scratch_bytes < vsr_conv_layer_bwd_scratch_bytes(dtype, N, H, W, pixel_shuffle)) return VSR_ERR_WORKSPACE;
+    if (pixel_shuffle && !layer_width_ok(cin_pm)) return VSR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const size_t es = esize(dtype);
     char* wp = (char*)scratch;
@@ -1534,46 +1624,48 @@ int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
         else if (act == ACT_NONE) CK(vsr_launch_planar_to_pm(dtype, dy_planar, dym, N, 2, H, W, 16, st));
         else return VSR_ERR_UNSUPPORTED;
     } else if (act != ACT_NONE) {
-        const int cdy = pixel_shuffle ? C : cd;
+        const int cdy = pixel_shuffle ? cin_pm : cd;
         CK(vsr_launch_mask_pm(dtype, dy_pm, y_pm, dym, mslope, (long long)N * pm_image_elems(sps * H, sps * W, cdy), st));
     }
     const void* dyM = (!dy_pm || act != ACT_NONE) ? (const void*)dym : dy_pm;
 
-    if (lr_planar) {                                       // stems: cat([lr(3), feat(64)]) or lr alone  (conv.py:97)
-        if (ks != 3 || cout_real != C || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
+    if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone  (conv.py:97), C = 16, 32 or 64
+        const int C = cout_real, CO = C < 32 ? 32 : C;
+        if (ks != 3 || !layer_width_ok(C) || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
         const bool cat = x_pm != nullptr;
         if ((cat && (cin_pm != C || cin_real != C + 3)) || (!cat && cin_real != 3)) return VSR_ERR_UNSUPPORTED;
         const int I_total = cat ? C + 3 : 3;
         if (cat && dx_pm) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, 9, C, C, C, C, I_total, 3, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W);
-            CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st));
+            CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, C, C, C, I_total, 3, 1, 0, 1, st));
+            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
+            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st));
         }
         if (dlr_planar) {
             CK(vsr_launch_pack_weights(dtype, w, wp, 9, 32, C, 3, C, I_total, 0, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dlr_planar, N, H, W);
+            ConvArgs a = plain64(dyM, wp, nullptr, dlr_planar, N, H, W, C);
             a.cout_real = 3; a.dst_nstride = (long long)3 * H * W;
-            CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 32, EPI_PLANAR, a, st));
+            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
         }
         if (gw) {
-            WgradArgs a = wg_base(N, H, W);
+            WgradArgs a = wg_base(N, H, W, C, C);
             a.x[0] = lr_planar; a.x_nstride = (long long)3 * H * W; a.dy[0] = dyM;
-            CK(wgrad(3, 16, true, 64, a, C, 3, I_total, 0, 1, 0, gb, 0));
+            CK(wgrad(3, 16, true, C, a, C, 3, I_total, 0, 1, 0, gb, 0));
             if (cat) {
-                WgradArgs b2 = wg_base(N, H, W);
+                WgradArgs b2 = wg_base(N, H, W, C, C);
                 b2.x[0] = x_pm; b2.dy[0] = dyM;
-                CK(wgrad(3, 64, false, 64, b2, C, C, I_total, 3, 1, 0, nullptr, 0));
+                CK(wgrad(3, C, false, C, b2, C, C, I_total, 3, 1, 0, nullptr, 0));
             }
         }
         return VSR_OK;
     }
     if (ks == 3 || ks == 1) {
-        if (cin_pm != C || cin_real != C || !x_pm) return VSR_ERR_UNSUPPORTED;
-        if (pixel_shuffle) {                               // conv3x3 64 -> 256 + PixelShuffle(2)  (upsampling.py:10-12)
+        const int C = cin_pm, CO = C < 32 ? 32 : C;
+        if (!layer_width_ok(C) || cin_real != C || !x_pm) return VSR_ERR_UNSUPPORTED;
+        if (pixel_shuffle) {                               // conv3x3 C -> 4C + PixelShuffle(2)  (upsampling.py:10-12)
             if (ks != 3 || cout_real != 4 * C || cd != C || act != ACT_NONE) return VSR_ERR_UNSUPPORTED;
             if (dx_pm) {
-                for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * C * C * es, 9, C, C, C, C, C, 0, 4, z, 1, st));
-                if (dtype == VSR_BF16) {
+                for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, 1, st));
+                if (dtype == VSR_BF16 && C == 64) {
                     for (int z = 0; z < 4; ++z) {          // phase z reads phase z-1's partial sum as its residual, in place
                         ConvArgs a = plain64(dyM, wp + (size_t)z * 9 * C * C * es, nullptr, dx_pm, N, H, W);
                         a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W; a.src_oy[0] = z >> 1; a.src_ox[0] = z & 1;
@@ -1582,31 +1674,31 @@ int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
                         CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st));
                     }
                 } else {
-                    ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W);
+                    ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
                     a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
                     for (int q = 0; q < 4; ++q) { a.src[q] = dyM; a.src_oy[q] = q >> 1; a.src_ox[q] = q & 1; a.src_nstride[q] = pm_image_elems(2 * H, 2 * W, C); }
-                    CK(vsr_launch_conv(dtype, 3, 4, 64, 64, 0, 64, EPI_NHWC, a, st));
+                    CK(vsr_launch_conv(dtype, 3, 4, C, C, 0, CO, EPI_NHWC, a, st));
                 }
             }
             if (gw)
                 for (int z = 0; z < 4; ++z) {
-                    WgradArgs a = wg_base(N, H, W);
+                    WgradArgs a = wg_base(N, H, W, C, C);
                     a.x[0] = x_pm; a.dy[0] = dyM;
                     a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C);
-                    CK(wgrad(3, 64, false, 64, a, C, C, C, 0, 4, z, gb, 0));
+                    CK(wgrad(3, C, false, C, a, C, C, C, 0, 4, z, gb, 0));
                 }
             return VSR_OK;
         }
         if (cout_real != C || cd != C) return VSR_ERR_UNSUPPORTED;
         if (dx_pm) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, C, C, C, C, C, 0, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W);
-            CK(vsr_launch_conv(dtype, ks, 1, 64, 64, 0, 64, EPI_NHWC, a, st));
+            CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, CO, C, C, C, C, 0, 1, 0, 1, st));
+            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
+            CK(vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st));
         }
         if (gw) {
-            WgradArgs a = wg_base(N, H, W);
+            WgradArgs a = wg_base(N, H, W, C, C);
             a.x[0] = x_pm; a.dy[0] = dyM;
-            CK(wgrad(ks, 64, false, 64, a, C, C, C, 0, 1, 0, gb, 0));
+            CK(wgrad(ks, C, false, C, a, C, C, C, 0, 1, 0, gb, 0));
         }
         return VSR_OK;
     }
@@ -1662,40 +1754,42 @@ int vsr_conv_layer_fwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
     ConvArgs a = {};
     a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1; a.out_step = 1; a.Hd = H; a.Wd = W;
     a.act = act; a.leaky_slope = slope; a.bias = bias; a.wpack = wpack;
-    if (lr_planar) {                                       // stems: cat([lr(3), feat(64)]) or lr alone
-        if (ks != 3 || cout_real != C || !y_pm || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
+    if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone, C = 16, 32 or 64
+        const int C = cout_real, CO = C < 32 ? 32 : C;
+        if (ks != 3 || !layer_width_ok(C) || !y_pm || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
         a.CD = C; a.cout_real = C; a.dst[0] = y_pm; a.dst_nstride = pm_image_elems(H, W, C);
         if (x_pm) {
             if (cin_pm != C || cin_real != C + 3) return VSR_ERR_UNSUPPORTED;
-            CK(vsr_launch_pack_weights(dtype, w, wp, 9, C, C, C, C, C + 3, 3, 1, 0, 0, st));
-            CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)9 * C * C * es, 9, C, 16, C, 3, C + 3, 0, 1, 0, 0, st));
+            CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, C, C, C, C + 3, 3, 1, 0, 0, st));
+            CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)9 * CO * C * es, 9, CO, 16, C, 3, C + 3, 0, 1, 0, 0, st));
             a.src[0] = x_pm; a.src_nstride[0] = pm_image_elems(H, W, C);
             a.src[1] = lr_planar; a.src_nstride[1] = (long long)3 * H * W;
-            return vsr_launch_conv(dtype, 3, 2, 64, 16, 1, 64, EPI_NHWC, a, st);
+            return vsr_launch_conv(dtype, 3, 2, C, 16, 1, CO, EPI_NHWC, a, st);
         }
         if (cin_real != 3) return VSR_ERR_UNSUPPORTED;
-        CK(vsr_launch_pack_weights(dtype, w, wp, 9, C, 16, C, 3, 3, 0, 1, 0, 0, st));
+        CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, 16, C, 3, 3, 0, 1, 0, 0, st));
         a.src[0] = lr_planar; a.src_nstride[0] = (long long)3 * H * W;
-        return vsr_launch_conv(dtype, 3, 1, 16, 16, 1, 64, EPI_NHWC, a, st);
+        return vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st);
     }
     a.src[0] = x_pm; a.src_nstride[0] = pm_image_elems(H, W, cin_pm);
     if (ks == 3 || ks == 1) {
-        if (cin_pm != C || cin_real != C) return VSR_ERR_UNSUPPORTED;
+        const int C = cin_pm, CO = C < 32 ? 32 : C;
+        if (!layer_width_ok(C) || cin_real != C) return VSR_ERR_UNSUPPORTED;
         if (pixel_shuffle) {
             if (ks != 3 || cout_real != 4 * C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-            for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * C * C * es, 9, C, C, C, C, C, 0, 4, z, 0, st));
+            for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, 0, st));
             // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c + 2i + j]: sub-conv z uses rows 4c+z and bias entries 4c+z
-            float* b4 = reinterpret_cast<float*>(wp + (size_t)4 * 9 * C * C * es);
+            float* b4 = reinterpret_cast<float*>(wp + (size_t)4 * 9 * CO * C * es);
             if (b) for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(VSR_F32, b, b4 + z * C, 1, C, 1, C, 1, 1, 0, 4, z, 0, st));
-            a.bias = b ? b4 : nullptr; a.bias_zstride = C; a.nz = 4; a.w_zstride = 9 * C * C;
+            a.bias = b ? b4 : nullptr; a.bias_zstride = C; a.nz = 4; a.w_zstride = 9 * CO * C;
             a.out_step = 2; a.Hd = 2 * H; a.Wd = 2 * W; a.CD = C; a.cout_real = C; a.dst_nstride = pm_image_elems(2 * H, 2 * W, C);
             for (int z = 0; z < 4; ++z) { a.dst[z] = y_pm; a.out_oy[z] = z >> 1; a.out_ox[z] = z & 1; }
-            return vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+            return vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st);
         }
         if (cout_real != C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-        CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, C, C, C, C, C, 0, 1, 0, 0, st));
+        CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, CO, C, C, C, C, 0, 1, 0, 0, st));
         a.CD = C; a.cout_real = C; a.dst[0] = y_pm; a.dst_nstride = pm_image_elems(H, W, C);
-        return vsr_launch_conv(dtype, ks, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+        return vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st);
     }
     if (ks != 7 || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
     for (int j = 0; j < NSPY; ++j) {

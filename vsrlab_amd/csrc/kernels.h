@@ -32,9 +32,9 @@ int vsr_launch_warp_fwd(int dtype, const void* in, const float* flow, void* out,
                         long long flow_nstride, hipStream_t st, int border = 0);
 int vsr_launch_warp_bwd(int dtype, const void* dout, const float* flow, float* dacc, int N, int H, int W, int C,
                         long long flow_nstride, hipStream_t st, int border = 0);
-// S: 64-bit fixed-point accumulator [N][H][W][64] (all-zero on entry and on exit)
+// S: 64-bit fixed-point accumulator [N][H][W][C] (all-zero on entry and on exit); C = 16, 32 or 64
 int vsr_launch_warp_bwd_gather(int dtype, const void* dout, const float* flow, const void* dtop, long long* S, int* far_count, void* out,
-                               int N, int H, int W, long long flow_nstride, hipStream_t st);
+                               int N, int H, int W, int C, long long flow_nstride, hipStream_t st);
 int vsr_launch_add_cast(int dtype, const void* a, const float* s, void* out, int N, int H, int W, int C, hipStream_t st);
 int vsr_launch_planar_to_pm(int dtype, const float* in, void* out, int N, int Cin, int H, int W, int C, hipStream_t st);
 int vsr_launch_pm_to_planar(int dtype, const void* in, float* out, int N, int Cout, int H, int W, int C, hipStream_t st);

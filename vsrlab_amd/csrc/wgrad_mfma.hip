@@ -757,7 +757,18 @@ extern "C" int vsr_debug_read_wclk(unsigned long long* host_out) {
     X(7, 64, false, 32, false)        /* 64->32 (bf16; fp32 runs it as two 32-channel halves: LDS) */ \
     X(7, 32, false, 32, false)        \
     X(7, 32, false, 16, false)        /* 32->16 */ \
-    X(7, 16, false, 16, false)        /* 16->2 (dY = masked flow gradient, 16-channel padded) */
+    X(7, 16, false, 16, false)        /* 16->2 (dY = masked flow gradient, 16-channel padded) */ \
+    /* mid_channels C = 16 / 32 (the narrow engine; the pixel-shuffle layers as four C->C phase launches) */ \
+    X(3, 16, false, 16, false)        /* trunk / upsample phases, C=16 */ \
+    X(3, 32, false, 32, false)        /* ... C=32 */ \
+    X(3, 16, true, 16, false)         /* stem LR part, cleaner stem, C=16 */ \
+    X(3, 16, true, 32, false)         /* ... C=32 */ \
+    X(1, 16, false, 16, false)        /* point_conv halves */ \
+    X(1, 32, false, 32, false)        \
+    X(3, 16, false, 64, false)        /* conv_last.0 C->64 */ \
+    X(3, 32, false, 64, false)        \
+    X(3, 16, false, 16, true)         /* cleaner out conv C->3 (planar dY) */ \
+    X(3, 32, false, 16, true)
 
 int vsr_launch_wgrad7x7_pc(int cx, int cout, const WgradArgs& a, int max_slabs, int* nslabs, hipStream_t st);   // wgrad7x7_pc.hip
 

@@ -284,11 +284,23 @@ class _ResidualConvFn(torch.autograd.Function):
         return from_pixel_major(gx), gw1, gb1, gw2, gb2, None
 
 
+MID_CHANNELS = (16, 32, 64)          # the widths of the HIP path: 64 on the whole-path entries, 16 / 32 on the narrow ones
+
+
+def _check_width(c: int, what: str) -> None:
+    if c not in MID_CHANNELS:
+        raise NotImplementedError(f"the HIP {what} is built for mid_channels 16, 32 or 64, not {c}")
+
+
 def residual_conv(x, w1, b1, w2, b2, compute_dtype: Optional[str] = None):
     _require_gpu(x)
-    if x.shape[1] != 64:
-        raise NotImplementedError("the HIP ResidualConv is built for 64 channels (the reference default)")
-    return _ResidualConvFn.apply(x, w1, b1, w2, b2, resolve_dtype(compute_dtype))
+    c = x.shape[1]
+    _check_width(c, "ResidualConv")
+    if c == 64:
+        return _ResidualConvFn.apply(x, w1, b1, w2, b2, resolve_dtype(compute_dtype))
+    # 16 / 32 channels: the two convs as vsr_conv_layer_fwd / _bwd layers, the identity added by autograd
+    a = _conv_layer_autograd(x, None, w1, b1, 1, compute_dtype=compute_dtype)
+    return x + _conv_layer_autograd(a, None, w2, b2, 0, compute_dtype=compute_dtype)
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -458,21 +470,30 @@ class _CtxToken:
     """weakref-able handle tying a workspace to the lifetime of an autograd graph node."""
 
 
+def _engine_entries(mid_channels: int):
+    """The C entries of the BasicVSR engine for a width: vsr_basicvsr_* (64) or vsr_basicvsr_narrow_* (16, 32)."""
+    _check_width(mid_channels, "BasicVSR engine")
+    lib = _lib.load()
+    pre = "vsr_basicvsr_" if mid_channels == 64 else "vsr_basicvsr_narrow_"
+    return {k: getattr(lib, pre + k) for k in ("workspace_bytes", "forward", "backward", "get_flows")}
+
+
 class _BasicVSRFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lrs, desc_tuple, pool, n_trainable, need_bwd, direct, *params):
         n, t, h, w, mid, rb, up, dtype, arena = desc_tuple
         desc = BasicVSRDesc(n, t, h, w, mid, rb, up, dtype, arena)
         lib = _lib.load()
-        nbytes = lib.vsr_basicvsr_workspace_bytes(ctypes.byref(desc), int(need_bwd))
+        E = _engine_entries(mid)
+        nbytes = E["workspace_bytes"](ctypes.byref(desc), int(need_bwd))
         if nbytes == 0:
             raise RuntimeError(f"vsrlab_amd: unsupported BasicVSR configuration for the HIP path: {desc_tuple}")
         ws = pool.acquire((desc_tuple, need_bwd, lrs.device.index), nbytes, lrs.device)
         lr32 = _f32c(lrs)
         ps = [_f32c(p) for p in params]
         sr = torch.empty((n, t, 3, up * h, up * w), dtype=torch.float32, device=lrs.device)
-        _lib.check(lib.vsr_basicvsr_forward(ctypes.byref(desc), _ptr_array(ps), len(ps), _ptr(lr32), _ptr(sr), _ptr(ws.buf),
-                                            ws.buf.numel(), int(need_bwd), _stream()), "basicvsr_forward")
+        _lib.check(E["forward"](ctypes.byref(desc), _ptr_array(ps), len(ps), _ptr(lr32), _ptr(sr), _ptr(ws.buf),
+                                ws.buf.numel(), int(need_bwd), _stream()), "basicvsr_forward")
         if need_bwd:
             token = _CtxToken()
             ctx.token = token
@@ -528,8 +549,8 @@ class _BasicVSRFn(torch.autograd.Function):
             else:
                 dest.append(flat[offs[k]:offs[k] + sizes[k]].view(p.shape))
         dlrs = torch.empty_like(ctx.lr32) if ctx.needs_input_grad[0] else None      # gradient w.r.t. the clip (need_bwd == 2)
-        _lib.check(lib.vsr_basicvsr_backward(ctypes.byref(desc), _ptr_array(ps), _ptr_array(dest), len(ps), _ptr(ctx.lr32),
-                                             _ptr(_f32c(dsr)), _ptr(dlrs), _ptr(ctx.ws.buf), ctx.ws.buf.numel(), _stream()),
+        _lib.check(_engine_entries(mid)["backward"](ctypes.byref(desc), _ptr_array(ps), _ptr_array(dest), len(ps), _ptr(ctx.lr32),
+                                                    _ptr(_f32c(dsr)), _ptr(dlrs), _ptr(ctx.ws.buf), ctx.ws.buf.numel(), _stream()),
                    "basicvsr_backward")
         ctx.consumed = True
         ctx.ws.owner = None
@@ -582,6 +603,7 @@ def basicvsr_forward(lrs: torch.Tensor, params: Sequence[torch.Tensor], n_traina
     _require_gpu(lrs)
     if lrs.dim() != 5 or lrs.shape[2] != 3:
         raise ValueError("lrs must be (n,t,3,h,w)")
+    _check_width(mid_channels, "BasicVSR engine")
     n, t, _, h, w = lrs.shape
     desc_tuple = (n, t, h, w, mid_channels, res_blocks, upscale, resolve_dtype(compute_dtype), arena_mode())
     # grad mode is off inside Function.forward, so decide here whether activations must be retained
@@ -604,8 +626,7 @@ def basicvsr_flows(lrs_shape, mid_channels, res_blocks, upscale, ws: Workspace, 
     desc = BasicVSRDesc(n, t, h, w, mid_channels, res_blocks, upscale, dtype)
     ff = torch.empty((n, t - 1, 2, h, w), dtype=torch.float32, device=device)
     fb = torch.empty_like(ff)
-    lib = _lib.load()
-    _lib.check(lib.vsr_basicvsr_get_flows(ctypes.byref(desc), _ptr(ws.buf), _ptr(ff), _ptr(fb), _stream()), "get_flows")
+    _lib.check(_engine_entries(mid_channels)["get_flows"](ctypes.byref(desc), _ptr(ws.buf), _ptr(ff), _ptr(fb), _stream()), "get_flows")
     return ff, fb
 
 
@@ -622,7 +643,10 @@ class _CleanerFn(torch.autograd.Function):
         lib = _lib.load()
         ps = [_f32c(p) for p in params]
         lr32 = _f32c(lr)
-        nbytes = lib.vsr_cleaner_workspace_bytes(n * t, h, w, blocks, steps, dtype, int(need_bwd))
+        if mid_channels == 64:
+            nbytes = lib.vsr_cleaner_workspace_bytes(n * t, h, w, blocks, steps, dtype, int(need_bwd))
+        else:
+            nbytes = lib.vsr_cleaner_narrow_workspace_bytes(n * t, h, w, mid_channels, blocks, steps, dtype, int(need_bwd))
         if nbytes == 0:
             raise RuntimeError("vsrlab_amd: unsupported pre-clean configuration for the HIP path")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=lr.device)
@@ -663,6 +687,7 @@ def cleaner_forward(params: Sequence[torch.Tensor], lr: torch.Tensor, mid_channe
     n, t, c, h, w = lr.shape
     if c != 3:
         raise ValueError("lr must be (n,t,3,h,w)")
+    _check_width(mid_channels, "pre-clean stack")
     need_bwd = torch.is_grad_enabled() and (lr.requires_grad or any(p.requires_grad for p in params))
     return _CleanerFn.apply(lr, (mid_channels, blocks, steps, resolve_dtype(compute_dtype), need_bwd), *params)
 
@@ -994,7 +1019,7 @@ def conv_layer(x_pm: Optional[torch.Tensor], weight: torch.Tensor, bias: Optiona
     if planar_out:
         y_pl = torch.empty((n, cout, h, w), dtype=torch.float32, device=dev)
     else:
-        cd = 64 if pixel_shuffle else max(16, cout)
+        cd = cout // 4 if pixel_shuffle else max(16, cout)
         s = 2 if pixel_shuffle else 1
         y_pm = torch.empty((n, s * h, (s * w + 31) // 32, cd // 8, 32, 8), dtype=_TORCH_DT[dt], device=dev)
         y_pm.pm_w = s * w
@@ -1024,7 +1049,7 @@ class _ConvLayerFn(torch.autograd.Function):
                     x_pm.pm_w if x_pm is not None else None, bias is not None)
         if planar_out:
             return y
-        return from_pixel_major(y, 64 if pixel_shuffle else cout)
+        return from_pixel_major(y, cout // 4 if pixel_shuffle else cout)
 
     @staticmethod
     def backward(ctx, dout):
@@ -1035,7 +1060,7 @@ class _ConvLayerFn(torch.autograd.Function):
         if x_pm is not None:
             x_pm.pm_w = xw
         need_x, need_lr, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        cd = 0 if planar else (64 if ps else max(16, cout))
+        cd = 0 if planar else (cout // 4 if ps else max(16, cout))
         dy_pm = dy_pl = y_pm = y_pl = None
         if planar:
             dy_pl, y_pl = _f32c(dout), y
@@ -1084,11 +1109,12 @@ def spynet_module_forward(x: torch.Tensor, params: Sequence[torch.Tensor], last_
 
 
 def pixel_shuffle_pack_forward(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], compute_dtype: Optional[str] = None):
-    """PixelShufflePack.forward (upsampling.py:10-12): conv3x3 64 -> 256 + PixelShuffle(2); the shuffle is the store pattern;
-    differentiable."""
+    """PixelShufflePack.forward (upsampling.py:10-12): conv3x3 C -> 4C + PixelShuffle(2), C = 16, 32 or 64; the shuffle is the
+    store pattern; differentiable."""
     _require_gpu(x)
-    if x.shape[1] != 64 or tuple(weight.shape) != (256, 64, 3, 3):
-        raise NotImplementedError("the HIP PixelShufflePack is built for 64 -> 64 channels, scale 2 (the reference's use)")
+    c = x.shape[1]
+    if c not in MID_CHANNELS or tuple(weight.shape) != (4 * c, c, 3, 3):
+        raise NotImplementedError("the HIP PixelShufflePack is built for C -> C channels, scale 2 (the reference's use), C = 16, 32 or 64")
     return _conv_layer_autograd(x, None, weight, bias, 0, pixel_shuffle=True, compute_dtype=compute_dtype)
 
 
@@ -1099,12 +1125,15 @@ def residual_block_forward(x: torch.Tensor, stem_w: torch.Tensor, stem_b: torch.
     vsr_conv_layer_bwd, the blocks through the ResidualConv function)."""
     _require_gpu(x)
     n, cin, h, w = x.shape
-    if cin == 67:
+    mid = stem_w.shape[0]
+    if mid not in MID_CHANNELS:
+        raise NotImplementedError(f"the HIP ResidualBlock is built for mid_channels 16, 32 or 64, not {mid}")
+    if cin == 3 + mid:
         y = _conv_layer_autograd(x[:, 3:].contiguous(), x[:, :3].contiguous(), stem_w, stem_b, 2, compute_dtype=compute_dtype)
     elif cin == 3:
         y = _conv_layer_autograd(None, x, stem_w, stem_b, 2, compute_dtype=compute_dtype)
     else:
-        raise NotImplementedError("the HIP ResidualBlock stem takes 3 (pre-clean) or 3 + 64 (trunk) input channels")
+        raise NotImplementedError(f"the HIP ResidualBlock stem takes 3 (pre-clean) or 3 + {mid} (trunk) input channels")
     for (w1, b1, w2, b2) in blocks:
         y = residual_conv(y, w1, b1, w2, b2, compute_dtype)
     return y

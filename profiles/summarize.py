@@ -59,7 +59,7 @@ def main():
                     out["csrc_sha1"], out["git_head"] = tree.get("csrc_sha1"), tree.get("git_head")
         except OSError:
             pass
-    # ---- in-kernel clock of the dominant kernel: tools/ab_chain.py with the ABL=0 diagnostic build (s_memtime / s_memrealtime around
+    # ---- in-kernel clock of the dominant kernel: tools/ab_chain.py with the clock build, make CLOCK=1 (s_memtime / s_memrealtime around
     # the kernel, median over workgroups; MI355X_MICROARCH "DVFS give-back" item 6), same box and call as the traces ----
     try:
         import re

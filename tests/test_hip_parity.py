@@ -1253,16 +1253,16 @@ except RuntimeError as e:
 """
 
 
-def test_a_real_chain_timeout_is_loud_in_a_subprocess():
-    """The same failure through the REAL path: the diagnostic build `make ABL=8 ABLSRC=conv3x3_chain` (bit 3: the MFMA waves never
-    publish their tiles) makes every dependency wait of a layer > 0 run into its 1 s clock.  A forward through that library must
+def test_a_real_chain_timeout_is_loud_on_the_nopublish_library():
+    """The same failure through the REAL path: the test library libvsrlab_hip_chain_nopublish.so (VSR_TEST_CHAIN_NO_PUBLISH: the MFMA
+    waves never publish their tiles) makes every dependency wait of a layer > 0 run into its 1 s clock.  A forward through that library must
     drain (no hang), count its give-ups, return a non-finite sr, and functional.raise_on_chain_timeout must raise."""
     _gpu()
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "vsrlab_amd", "lib", "libvsrlab_hip_conv3x3_chain_abl8.so")
-    assert os.path.exists(lib), "build() makes the diagnostic chain library (make ABL=8 ABLSRC=conv3x3_chain)"
+    lib = os.path.join(root, "vsrlab_amd", "lib", "libvsrlab_hip_chain_nopublish.so")
+    assert os.path.exists(lib), "build() makes the test chain library (the Makefile's default target)"
     env = dict(os.environ, VSRLAB_AMD_LIB=lib)
     r = subprocess.run([sys.executable, "-c", _TIMEOUT_CHILD.format(root=root)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

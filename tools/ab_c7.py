@@ -4,7 +4,7 @@ inside the timed region).
 
     python tools/ab_c7.py [rounds] lib_a.so lib_b.so ...      (paths relative to vsrlab_amd/lib/)
 
-Diagnostic builds (make ABL=<bits> ABLSRC=conv7x7_persist) also report the in-kernel clock of the last launch."""
+The clock build (make -C vsrlab_amd/csrc CLOCK=1: libvsrlab_hip_clock.so) also reports the in-kernel clock of the last launch."""
 import ctypes
 import os
 import sys

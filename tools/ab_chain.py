@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """The trunk-chain kernel (csrc/conv3x3_chain.hip) on bench.py's roofline-leg workload, for one or more builds of the library:
 
-    python tools/ab_chain.py [lib.so ...]        (default: the ABL=0 diagnostic build, which carries the in-kernel clock)
+    python tools/ab_chain.py [lib.so ...]        (default: libvsrlab_hip_clock.so, the clock build)
 
 Each build runs in a child process (the library path is fixed at import: VSRLAB_AMD_LIB).  Prints the launch time per layer
-and, for diagnostic builds (make ABL=<bits> ABLSRC=conv3x3_chain), the in-kernel clock: s_memtime / s_memrealtime around the
+and, for the clock build (make -C vsrlab_amd/csrc CLOCK=1), the in-kernel clock: s_memtime / s_memrealtime around the
 whole kernel, median over workgroups -- cycles per workgroup and GHz (MI355X_MICROARCH "DVFS give-back" item 6)."""
 import os
 import subprocess
@@ -50,7 +50,7 @@ if __name__ == "__main__":
     if os.environ.get("AB_CHAIN_CHILD"):
         child()
         sys.exit(0)
-    libs = sys.argv[1:] or [os.path.join(ROOT, "vsrlab_amd", "lib", "libvsrlab_hip_conv3x3_chain_abl0.so")]
+    libs = sys.argv[1:] or [os.path.join(ROOT, "vsrlab_amd", "lib", "libvsrlab_hip_clock.so")]
     for lib in libs:
         env = dict(os.environ, AB_CHAIN_CHILD="1", VSRLAB_AMD_LIB=os.path.abspath(lib))
         r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env)

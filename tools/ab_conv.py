@@ -5,8 +5,8 @@ process, on random data, out of cache).
 
 Every library is loaded side by side (ctypes); each round times `iters` launches of every library back to back: the two trunk
 epilogues (bias+ReLU with sign-bit output is not reachable through this entry point, so: bias+ReLU / bias+skip) over 8 rotating
-buffer sets (1.6 GB, beyond the Infinity Cache).  Diagnostic builds (make ABL=<bits>) also report the in-kernel clock
-(s_memtime / s_memrealtime of the last launch, median over workgroups)."""
+buffer sets (1.6 GB, beyond the Infinity Cache).  The clock build (make -C vsrlab_amd/csrc CLOCK=1: libvsrlab_hip_clock.so) also
+reports the in-kernel clock (s_memtime / s_memrealtime of the last launch, median over workgroups)."""
 import ctypes
 import os
 import sys

@@ -1,6 +1,9 @@
 """Interleaved A/B of builds of the 3x3 64->64 weight-gradient kernel (7 frames of 540x960 per launch, as inside a step).
 
-    python tools/ab_wgrad.py [rounds] lib_a.so lib_b.so ...      (paths relative to vsrlab_amd/lib/)"""
+    python tools/ab_wgrad.py [rounds] lib_a.so lib_b.so ...      (paths relative to vsrlab_amd/lib/)
+
+The clock build (make -C vsrlab_amd/csrc CLOCK=1: libvsrlab_hip_clock.so) also reports the in-kernel clock, the cycles per workgroup
+and the consumers' barrier wait."""
 import ctypes
 import os
 import sys

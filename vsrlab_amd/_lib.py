@@ -8,7 +8,7 @@ import os
 from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# VSRLAB_AMD_LIB: another build of the same library (the diagnostic `make ABL=...` / `make STAMPS=1` builds), for whole-step A/B runs
+# VSRLAB_AMD_LIB: another build of the same library (the clock build `make CLOCK=1`, or a parent commit's), for whole-step A/B runs
 LIB_PATH = os.environ.get("VSRLAB_AMD_LIB") or os.path.join(_HERE, "lib", "libvsrlab_hip.so")
 
 DT_F32 = 0

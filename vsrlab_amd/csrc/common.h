@@ -183,7 +183,7 @@ static inline int vsr_num_cus() {
 // exactly once, also under concurrent first calls (the library is callable from several threads), and no launch path calls getenv.
 #include <cstdlib>
 struct VsrEnvSwitches {
-    bool generic_conv, generic_wgrad, attn_generic, single_stream;
+    bool generic_conv, generic_wgrad, single_stream;
     int wide2_max_wg;
 };
 static inline const VsrEnvSwitches& vsr_env() {
@@ -192,7 +192,6 @@ static inline const VsrEnvSwitches& vsr_env() {
         VsrEnvSwitches v;
         v.generic_conv = on("VSRLAB_AMD_GENERIC_CONV");
         v.generic_wgrad = on("VSRLAB_AMD_GENERIC_WGRAD");
-        v.attn_generic = getenv("VSRLAB_AMD_ATTN_GENERIC") != nullptr;
         v.single_stream = on("VSRLAB_AMD_SINGLE_STREAM");
         const char* e = getenv("VSRLAB_AMD_WIDE2_MAX_WG");
         v.wide2_max_wg = e ? atoi(e) : 0;

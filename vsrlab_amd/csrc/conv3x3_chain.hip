@@ -55,41 +55,16 @@ constexpr int IN_CHUNKS = PNPIX * 8;
 constexpr int NPIECE_T = (IN_CHUNKS + 63) / 64;
 constexpr int NPIECE_W = (NPIECE_T + 3) / 4;                              // 11; the leader wave (w4 = 0) always issues exactly 11
 
-// Diagnostic build only (make ABL=<bits> ABLSRC=conv3x3_chain; results may be WRONG, only the run time is read): bit 0: plain
-// instead of write-through stores; bit 1: plain instead of sc1 loads; bit 2: no dependency waits (every item counts as ready);
-// bit 3: no publishes; bit 4: no wait for the previous tile's stores at the top of an epilogue without operands; bit 5: no fragment
-// reads after step 0 (bare MFMA loop); bit 6: the producers issue only their first tile (no DMA); bit 7: no output stores; bit 11: every fragment read
-// of a tile re-reads the first K step's addresses (the LDS reads stay, the operands stop changing); bit 12: epilogue = convert + store; bit 13 / 14: no A (weight) / no B (pixel)
-// fragment reads after the first K step (what weights held in registers would save); bit 15: the weight image in LDS in MFMA-fragment
-// order (every A read = 1 KiB contiguous) instead of [cout row][8 swizzled chunks] -- same results, an energy experiment; bit 16: no A
-// (weight) fragment reads for the taps of kernel row ky = 1 (the upper bound of what holding that row's 24 fragments = 96 registers
-// per lane in registers would save: round-3 VERDICT next #1a); bit 17: only the first 8 of the 18 K steps = 128 of 288 MFMAs and
-// 64 of 144 fragment reads per tile and wave (the matrix work of a Winograd F(2x2, 3x3) kernel WITHOUT its transforms: VERDICT #1c);
-// bit 18: a new layer's weights are loaded at the layer change itself (round 3's exposed L2 round trip) instead of a tile ahead.  On the
-// back-to-back leg the kernel's time is its energy, so these price the energy of LDS reads / DMA / stores.
-#ifdef VSR_ABL
-#define CABL(bit) ((VSR_ABL >> (bit)) & 1)
+// The energy of the LDS reads, DMA and stores was priced with ablated builds of this file: DESIGN 4.1c.
+#ifdef VSR_CLOCK
 __device__ unsigned long long g_clk_chain[256 * 2];      // [workgroup][cycles, 100 MHz ticks] of the last chain launch
-#else
-#define CABL(bit) 0
 #endif
-#if CABL(0)
-#define CH_SC1_ST ""
-#elif CABL(8)
-#define CH_SC1_ST " sc1 nt"
-#elif CABL(9)
-#define CH_SC1_ST " nt"
-#elif CABL(10)
-#define CH_SC1_ST " sc0 sc1"
+// Test build only (libvsrlab_hip_chain_nopublish.so): the MFMA waves never publish their tiles, so every dependency wait runs
+// into its 1 s bound -- the real timeout path that test_a_real_chain_timeout_is_loud_on_the_nopublish_library drives.
+#ifdef VSR_TEST_CHAIN_NO_PUBLISH
+#define CHAIN_PUBLISH 0
 #else
-#define CH_SC1_ST " sc1"
-#endif
-#if CABL(1)
-#define CH_SC1_LD ""
-#define CH_AUX 0
-#else
-#define CH_SC1_LD " sc1"
-#define CH_AUX 16
+#define CHAIN_PUBLISH 1
 #endif
 __device__ uint4 g_chain_zero_chunk[2];
 __device__ unsigned g_chain_timeouts;           // waits given up since the module was loaded (never reset: vsr_debug_chain_timeouts)
@@ -110,7 +85,7 @@ __device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) { unsi
 
 #define GLDS16_SC1(src, dst)                                                                          \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, CH_AUX)
+                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, 16)
 #define GP(T, x) ((__attribute__((address_space(1))) T*)(x))
 
 // The 3 x 3 tiles around (ty, tx) of one layer's image have been published by all four of their MFMA waves: flg points at the
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
     gu32* const qown = work + 64 + 16 * own;                               // this region's hand-out counter (a 64-byte line of its own)
     gu32* const flg0 = work + 256;                                         // [item = layer * tiles + tile][4 MFMA waves]
 
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     unsigned long long clk_t0 = 0, clk_r0 = 0;
     if (tid == 0) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -217,7 +192,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
             int* sl = ctl + 8 * sidx;
             if (it >= 0) {
                 const int l = it / tiles, r = it - l * tiles, n = r / per, r2 = r - n * per, ty = r2 / ntx;
-                sl[0] = it; sl[1] = l; sl[2] = n; sl[3] = ty; sl[4] = r2 - ty * ntx; sl[5] = (l == 0 || CABL(2)) ? 1 : 0;
+                sl[0] = it; sl[1] = l; sl[2] = n; sl[3] = ty; sl[4] = r2 - ty * ntx; sl[5] = l == 0 ? 1 : 0;
             } else {
                 sl[0] = -1; sl[1] = 0; sl[2] = 0; sl[3] = 0; sl[4] = 0; sl[5] = 0;
             }
@@ -236,7 +211,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
     _Pragma("unroll") for (int i = 0; i < WCH; ++i) {                                                                    \
         const int idx = (tid & 255) + i * 256;                                                                           \
         const int tap = idx >> 9, r = (idx >> 3) & 63, c = idx & 7;                                                      \
-        *reinterpret_cast<u32x4_t*>(lds_w + (CABL(15) ? ((((tap * 2 + (c >> 2)) * 4 + (r >> 4)) * 64 + (c & 3) * 16 + (r & 15)) * 16) : tap * 8192 + (r * 8 + (c ^ ((r >> 1) & 7))) * 16)) = wv[i]; \
+        *reinterpret_cast<u32x4_t*>(lds_w + tap * 8192 + (r * 8 + (c ^ ((r >> 1) & 7))) * 16) = wv[i];                 \
     }
     constexpr int WCH = 9 * 64 * 8 / 256;
 
@@ -285,7 +260,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
         // item 0: nothing was polled for it yet
         {
             const int l0 = ctl[1], n0 = ctl[2], ty0 = ctl[3], tx0 = ctl[4];
-            if (l0 > 0 && !CABL(2)) (void)halo_wait(flg0 + 4 * ((long long)(l0 - 1) * tiles + (long long)n0 * per), ty0, tx0, nty, ntx, lane, err);
+            if (l0 > 0) (void)halo_wait(flg0 + 4 * ((long long)(l0 - 1) * tiles + (long long)n0 * per), ty0, tx0, nty, ntx, lane, err);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             issue(l0, n0, ty0, tx0, 0);
         }
@@ -304,13 +279,6 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 // the weight image is free (every MFMA wave is past the K loop of the previous tile: the barrier that ended it).
                 // Before, the MFMA waves loaded, waited and wrote here, with the L2 round trip exposed once per layer and workgroup.
                 cur_layer = layer_k;
-                if (CABL(18)) {                                        // (diagnostic: the loads exposed here, as in round 3)
-                    const auto* wgx = GP(const u32x4_t, base + (unsigned long long)ka.layer[layer_k].w * 256ull);
-                    W_LOAD(wvp, wgx)
-                    const unsigned bo = ka.layer[layer_k].bias;
-                    bvp = 0.f;
-                    if (pt < 64 && bo != 0xffffffffu) bvp = GP(const float, base + (unsigned long long)bo * 256ull)[pm_acc_chan(pt >> 4, pt & 15)];
-                }
                 W_STORE(wvp)
                 if (pt < 64) reinterpret_cast<float*>(smem + BIAS_OFF)[pt] = bvp;
                 __syncthreads();
@@ -320,7 +288,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
             // the next item opens a new layer: its 72 KiB of packed weights (18 x 16 bytes per producer thread) and its bias are
             // requested now, the OLDEST vector-memory operations of this iteration (the leader's counted wait below looks at the
             // youngest ones only); they are written to LDS at the top of the next iteration
-            if (it1 >= 0 && !CABL(18)) {
+            if (it1 >= 0) {
                 const int l1w = __builtin_amdgcn_readfirstlane(s1[1]);
                 if (l1w != cur_layer) {
                     const auto* wgx = GP(const u32x4_t, base + (unsigned long long)ka.layer[l1w].w * 256ull);
@@ -343,7 +311,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                     if (leader && lane == 0) s1[5] = 1;   // tells the MFMA waves that their deferred publish cannot be what we wait for
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (!CABL(6)) issue(l1, n1, ty1, tx1, (k + 1) & 1);
+                issue(l1, n1, ty1, tx1, (k + 1) & 1);
             }
             if (leader) {
                 int* s2 = ctl + 8 * ((k + 2) % 3);
@@ -359,7 +327,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                         l2 = it2 / tiles; const int r = it2 - l2 * tiles; n2 = r / per; const int r2 = r - n2 * per; ty2 = r2 / ntx; tx2 = r2 - ty2 * ntx;
                         // its dependencies, looked at now, used a barrier later (the result returns behind this wave's DMA pieces,
                         // i.e. under the wait for the tile that is needed anyway)
-                        ok2 = l2 == 0 || CABL(2) || halo_ready(flg0 + 4 * ((long long)(l2 - 1) * tiles + (long long)n2 * per), ty2, tx2, nty, ntx, lane);
+                        ok2 = l2 == 0 || halo_ready(flg0 + 4 * ((long long)(l2 - 1) * tiles + (long long)n2 * per), ty2, tx2, nty, ntx, lane);
                     }
                 }
                 if (lane == 0) { s2[0] = it2; s2[1] = l2; s2[2] = n2; s2[3] = ty2; s2[4] = tx2; s2[5] = ok2 ? 1 : 0; }
@@ -377,7 +345,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
         unsigned a_lo[2], a_hi[2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            a_lo[kk] = CABL(15) ? (unsigned)((q * 16 + l15) * 16 + kk * 4096) : (unsigned)((l15 * 8 + ((4 * kk + q) ^ ((l15 >> 1) & 7))) * 16);
+            a_lo[kk] = (unsigned)((l15 * 8 + ((4 * kk + q) ^ ((l15 >> 1) & 7))) * 16);
             a_hi[kk] = a_lo[kk] + 6 * 8192;
         }
         const int b_lane = w4 * 2 * (PTWH * 128) + q * (PTWH * 16) + pxl * 16;
@@ -458,14 +426,14 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                         // (inline asm is not padded by hipcc: `s_nop 4` = the wait states between the scalar adds that made rbase and a
                         // vector-memory instruction using it as its base; cdna_hip_programming.md 5.7 item 2)
                         if (full) {
-                            if (nb == 0) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" CH_SC1_LD : "=v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
-                            else asm volatile("global_load_dwordx4 %0, %1, %2" CH_SC1_LD : "=v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
-                            asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" CH_SC1_LD : "=v"(rr[1][nb]) : "v"(lo), "s"(rbase) : "memory");
+                            if (nb == 0) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1" : "=v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
+                            else asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
+                            asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048 sc1" : "=v"(rr[1][nb]) : "v"(lo), "s"(rbase) : "memory");
                         } else {
                             rr[0][nb] = u32x4_t{0u, 0u, 0u, 0u}; rr[1][nb] = u32x4_t{0u, 0u, 0u, 0u};
                             if (ok[nb]) {
-                                asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" CH_SC1_LD : "+v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
-                                asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" CH_SC1_LD : "+v"(rr[1][nb]) : "v"(lo), "s"(rbase) : "memory");
+                                asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1" : "+v"(rr[0][nb]) : "v"(lo), "s"(rbase) : "memory");
+                                asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048 sc1" : "+v"(rr[1][nb]) : "v"(lo), "s"(rbase) : "memory");
                             }
                         }
                     }
@@ -474,8 +442,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 bf16x8_t fa[2][4], fb[2][4];
                 const unsigned bb = (unsigned)(W_BYTES + cur * IN_BYTES + b_lane);
 #define DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
-#define CV_LOADA(tap_, kk_, slot, mb) if (!((CABL(5) || CABL(13)) && tap_ + kk_ > 0) && !(CABL(16) && tap_ >= 3 && tap_ <= 5)) DSR(fa[slot][mb], (CABL(11) ? a_lo[0] : (tap_ < 6 ? a_lo[kk_] : a_hi[kk_])), (CABL(11) ? 0 : (tap_ < 6 ? tap_ : tap_ - 6) * 8192) + (mb) * (CABL(15) ? 1024 : 2048));
-#define CV_LOADB(ky_, kx_, kk_, slot, nb) if (!((CABL(5) || CABL(14)) && ky_ + kx_ + kk_ > 0)) DSR(fb[slot][nb], bb, CABL(11) ? (((nb) >> 1)) * (PTWH * 128) + (((nb) & 1) * 16) * 16 : (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
+#define CV_LOADA(tap_, kk_, slot, mb) DSR(fa[slot][mb], tap_ < 6 ? a_lo[kk_] : a_hi[kk_], (tap_ < 6 ? tap_ : tap_ - 6) * 8192 + (mb) * 2048);
+#define CV_LOADB(ky_, kx_, kk_, slot, nb) DSR(fb[slot][nb], bb, (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
 #define CV_LOAD(s, slot)                                                                                               \
                 {                                                                                                      \
                     constexpr int tap_ = (s) / 2, kk_ = (s) % 2, ky_ = tap_ / 3, kx_ = tap_ % 3;                       \
@@ -506,11 +474,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 CV_LOAD(0, 0)
-                CV_STEP(0) CV_STEP(1) CV_STEP(2) CV_STEP(3) CV_STEP(4) CV_STEP(5) CV_STEP(6) CV_STEP(7)
-                if (!CABL(17)) {
-                CV_STEP(8)
+                CV_STEP(0) CV_STEP(1) CV_STEP(2) CV_STEP(3) CV_STEP(4) CV_STEP(5) CV_STEP(6) CV_STEP(7) CV_STEP(8)
                 CV_STEP(9) CV_STEP(10) CV_STEP(11) CV_STEP(12) CV_STEP(13) CV_STEP(14) CV_STEP(15) CV_STEP(16) CV_STEP(17)
-                }
 #undef CV_ML_A
 #undef CV_ML_B
 #undef CV_STEP
@@ -525,10 +490,10 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 // now its flag word may be set (R1: every storing wave drains, then publishes for itself)
                 // (the builtin, so that hipcc's scoreboard knows the queue is empty: behind an asm wait it would wait again, for the
                 // publishing atomic below, in front of the first use of the sign bits)
-                if (!(CABL(4) && V == CHAIN_RELU)) __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0) alone
+                __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0) alone
                 __builtin_amdgcn_sched_barrier(0);
                 if (pending) {
-                    if (lane == 0 && !CABL(3)) __hip_atomic_store(pend_cnt, 1u, RLX_AGENT);
+                    if (lane == 0 && CHAIN_PUBLISH) __hip_atomic_store(pend_cnt, 1u, RLX_AGENT);
                     pending = false;
                 }
                 if constexpr (HAS_RES) {
@@ -554,10 +519,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                                 for (int j = 0; j < 4; ++j) { v[j] = acc[2 * kq][nb][j]; v[4 + j] = acc[2 * kq + 1][nb][j]; }
                                 const unsigned wbits = kq ? sbits.y : sbits.x;
                                 unsigned ow[4];
-                                if (CABL(12)) {
-#pragma unroll
-                                    for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_bf16(v[2 * jj], v[2 * jj + 1]);
-                                } else if (V == CHAIN_RELU) {
+                                if (V == CHAIN_RELU) {
 #pragma unroll
                                     for (int jj = 0; jj < 4; ++jj) {
                                         ow[jj] = pk_max_i16(pk_bf16(v[2 * jj], v[2 * jj + 1]), 0u);
@@ -575,11 +537,10 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                                 // write-through: the next layer's tiles may be loaded on another XCD
                                 // (asm: `s_nop 1` behind a 16-byte store, or hipcc's next instruction may overwrite the data registers before
                                 // the store has read them; `s_nop 4` in front of the first user of the freshly added base; 5.7 items 1, 2)
-                                if (CABL(7)) asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-                                else if (kq == 0) {
-                                    if (nb == 0 || !decltype(FULL)::value) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2" CH_SC1_ST "\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
-                                    else asm volatile("global_store_dwordx4 %0, %1, %2" CH_SC1_ST "\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
-                                } else asm volatile("global_store_dwordx4 %0, %1, %2 offset:2048" CH_SC1_ST "\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
+                                if (kq == 0) {
+                                    if (nb == 0 || !decltype(FULL)::value) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
+                                    else asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
+                                } else asm volatile("global_store_dwordx4 %0, %1, %2 offset:2048 sc1\n\ts_nop 1" :: "v"(lo), "v"(o), "s"(db) : "memory");
                             }
                         }
                     }
@@ -595,7 +556,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
             // already seen that tile's dependencies complete, drain and publish now.
             if (nx_item < 0 || nx_ok == 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0 && !CABL(3)) __hip_atomic_store(pend_cnt, 1u, RLX_AGENT);
+                if (lane == 0 && CHAIN_PUBLISH) __hip_atomic_store(pend_cnt, 1u, RLX_AGENT);
                 pending = false;
             }
             __syncthreads();                               // the next tile has landed; everybody has finished reading `cur`
@@ -604,7 +565,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
             tyi = __builtin_amdgcn_readfirstlane(nx_ty); txi = __builtin_amdgcn_readfirstlane(nx_tx);
         }
     }
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     if (tid == 0 && blockIdx.x < 256) {
         g_clk_chain[blockIdx.x * 2 + 0] = __builtin_amdgcn_s_memtime() - clk_t0;
         g_clk_chain[blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
@@ -623,7 +584,7 @@ __global__ void chain_poison_kernel(const unsigned* err, unsigned short* last_im
 
 }  // namespace
 
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
 extern "C" int vsr_debug_read_clk_chain(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_clk_chain), sizeof(unsigned long long) * 256 * 2) == hipSuccess ? 0 : VSR_ERR_HIP;
 }

@@ -54,35 +54,10 @@ template <int ACT> __device__ __forceinline__ float p_act(float v, float slope) 
     return v;
 }
 
-// Diagnostic build only (make STAMPS=1): per-wave cycle sums of the phases of a tile.  The stamp values
-// go to a buffer of their own and never into an output.
-#ifdef VSR_STAMPS
-__device__ unsigned long long g_stamps[256 * 8 * 8];
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define STAMP(var) const unsigned long long var = stamp()
-#define STAMP_ADD(slot, a, b) st_sum[slot] += (b) - (a)
-#else
-#define STAMP(var)
-#define STAMP_ADD(slot, a, b)
-#endif
-
-// Diagnostic build only (make ABL=<bits>): ablations that bound what a restructuring could buy, and the in-kernel clock
-// (s_memtime / s_memrealtime around the whole kernel, lane 0 of wave 0, to a buffer of their own).  Results of an ablated
-// build are WRONG by construction; only its run time and clock are read.  bit 0: no B-fragment reads for ky = 2 (what
-// ky-shared B fragments would save); bit 1: no sign-bit output; bit 2: no A-fragment reads for ky = 2; bit 3: producers
-// issue only the first tile; bit 4: epilogue = convert + store only; bit 5: no epilogue stores; bit 6: no fragment reads
-// after step 0 (bare MFMA loop); bit 7: no lgkmcnt wait at the top of a step.
-#ifdef VSR_ABL
+// What a restructuring could buy was bounded with ablated builds of this file: DESIGN 4.1.  Clock build only (make CLOCK=1):
+// s_memtime / s_memrealtime around the whole kernel, lane 0 of wave 0, to a buffer of their own.
+#ifdef VSR_CLOCK
 __device__ unsigned long long g_clk[256 * 4];
-#define ABL(bit) ((VSR_ABL >> (bit)) & 1)
-#else
-#define ABL(bit) 0
 #endif
 
 __device__ __forceinline__ void tile_coords(int tile, int ntx, int nty, int& n, int& ty0, int& tx0) {
@@ -126,21 +101,14 @@ __device__ __forceinline__ unsigned pk_max_i16(unsigned a, unsigned b) { unsigne
 __device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-// Diagnostic bit 8: nt on the tile DMA; bit 9: nt on the output stores.  tools/bw_probe.hip streams reads at 6.4-7.0 TB/s with nt against
-// 5.7-6.2 without, and out of cache (tools/ab_conv.py, 8 rotating buffer sets) nt STORES take 7 % off a bias+ReLU launch (36.7 -> 34.0 us;
-// bias+skip 42.3 -> 41.5; nt loads: 36.2 / 44.3) -- but inside a step, applied to the outputs of >= 512 MB (the 16P tensors of the
-// reconstruction), the step is 0.2-0.7 ms SLOWER (124.6-124.9 -> 125.1-125.6 ms, three interleaved pairs): their consumers do find the
-// tail of such a tensor in the Infinity Cache.  Not used (r04).
-#ifdef VSR_ABL
-#define P_DMA_AUX (((VSR_ABL >> 8) & 1) ? 2 : 0)
-#define P_NT_STORE ((VSR_ABL >> 9) & 1)
-#else
-#define P_DMA_AUX 0
-#define P_NT_STORE 0
-#endif
+// Plain (not nt) tile DMA and output stores.  tools/bw_probe.hip streams reads at 6.4-7.0 TB/s with nt against 5.7-6.2 without, and
+// out of cache (tools/ab_conv.py, 8 rotating buffer sets) nt STORES took 7 % off a bias+ReLU launch (36.7 -> 34.0 us; bias+skip 42.3 ->
+// 41.5; nt loads: 36.2 / 44.3) -- but inside a step, applied to the outputs of >= 512 MB (the 16P tensors of the reconstruction), the
+// step was 0.2-0.7 ms SLOWER (124.6-124.9 -> 125.1-125.6 ms, three interleaved pairs): their consumers do find the tail of such a
+// tensor in the Infinity Cache (r04).
 #define GLDS16(src, dst)                                                                              \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, P_DMA_AUX)
+                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
 
 // Epilogue variants are compile-time: a runtime-selected epilogue serialises 16 load->use->store
 // chains per tile (measured: 14 us of a 71 us launch).
@@ -176,12 +144,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
     // 4-11 on the even pixels and lanes 0-3, 12-15 on the odd ones make every group hit 16 distinct 16-byte bank groups.
     const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
     char* lds_w = smem;
-#ifdef VSR_STAMPS
-    const unsigned long long st_begin = stamp();
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     char* lds_t = smem + W_BYTES;                                         // two tile buffers
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     unsigned long long clk_t0 = 0, clk_r0 = 0;
     if (tid == 0) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -266,24 +230,14 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
         int cur = 0;
         TileIter it;
         it.init(walk.first, walk.stride, ntx, nty);
-        STAMP(q0);
         if (it.tile < walk.end) issue(it, 0);              // first tile in flight while the MFMA waves stage the weights
-        STAMP(q1);
-        STAMP_ADD(1, st_begin, q0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(q3);
         __syncthreads();                                   // weights and the first tile are in LDS
-        STAMP_ADD(2, st_begin, q1); STAMP_ADD(4, q1, q3);
         while (it.tile < walk.end) {
-            STAMP(t0);
             it.advance(walk.stride, ntx, nty);
-            if (it.tile < walk.end && !ABL(3)) issue(it, cur ^ 1);
-            STAMP(p1);
+            if (it.tile < walk.end) issue(it, cur ^ 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            STAMP(p2);
             __syncthreads();
-            STAMP(p3);
-            STAMP_ADD(5, t0, p1); STAMP_ADD(6, p1, p2); STAMP_ADD(7, p2, p3);
             cur ^= 1;
         }
     } else {
@@ -294,7 +248,6 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
         // Operand lane l = (i = l & 15, q = l >> 4): A[cout 16 mb + i][8 channels 8q..8q+7], B[same 8 channels][pixel i].
         // Fragment addresses: A two lane bases per channel half (taps 0-5 / 6-8: the immediate is 16 bits) + immediates
         // (tap, mb); B ONE lane base + immediates (row, ky, kx, half, channel half) of the [row][chunk][34 px][16 B] image.
-        STAMP(m0);
         u32x4_t wv[WCH];
         W_LOAD(wv)
         unsigned a_lo[2], a_hi[2];
@@ -318,13 +271,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             }
         }
         W_STORE(wv)
-        STAMP(m1);
-        STAMP_ADD(6, m0, m1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                   // weights and the first tile are in LDS
-#ifdef VSR_STAMPS
-        st_sum[5] = stamp() - st_begin;                    // prologue of the MFMA waves (weights staged, first tile landed)
-#endif
         auto* const dst_z = GP(bf16_t, a.dstz);
         const auto* const res_z = GP(const bf16_t, a.resz);
         const auto* const aux_z = GP(const bf16_t, a.auxz);
@@ -347,12 +295,11 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
         for (int hb = 0; hb < 2; ++hb)
 #pragma unroll
             for (int j = 0; j < 8; ++j) idA[hb][j] = (bf16_t)((q == (l15 >> 2) && j == 4 * hb + (l15 & 3)) ? 1.f : 0.f);
-        constexpr bool RES_MFMA = HAS_RES && !ABL(4);
+        static_assert(!HAS_RES || ACT == ACT_NONE, "the residual goes in on the matrix cores, ahead of any activation");
 
         int cur = 0;
         TileIter it;
         for (it.init(walk.first, walk.stride, ntx, nty); it.tile < walk.end; it.advance(walk.stride, ntx, nty)) {
-            STAMP(t0);
             // epilogue operands, requested now, used after the K loop
             const int tile = it.tile, n = it.n, ty0 = it.ty * PTH, tx0 = it.tx * PTW;
             const long long tbase = a.unshuffle ? (long long)n * a.dst_nstride + pm_off(ty0 >> 1, tx0 >> 1, 0, a.Wd >> 1, 64)      // (tx0 >> 1: a multiple of 16)
@@ -382,7 +329,6 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                 if (full) { CV_OPERANDS(true) } else { CV_OPERANDS(ok[nb]) }
             }
 #undef CV_OPERANDS
-            STAMP(t1);
 
             f32x4_t acc[4][4];                                      // first written by step 0's MFMAs, whose C operand is the bias
 
@@ -393,9 +339,9 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             const unsigned bb = (unsigned)(W_BYTES + cur * IN_BYTES + b_lane);   // B base of this tile's buffer
 #define DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
 #define CV_LOADA(tap_, kk_, slot, mb)                                                                                  \
-            if (!(ABL(2) && tap_ >= 6) && !(ABL(6) && tap_ + kk_ > 0)) DSR(fa[slot][mb], (tap_ < 6 ? a_lo[kk_] : a_hi[kk_]), (tap_ < 6 ? tap_ : tap_ - 6) * 8192 + (mb) * 2048);
+            DSR(fa[slot][mb], (tap_ < 6 ? a_lo[kk_] : a_hi[kk_]), (tap_ < 6 ? tap_ : tap_ - 6) * 8192 + (mb) * 2048);
 #define CV_LOADB(ky_, kx_, kk_, slot, nb)                                                                              \
-            if (!(ABL(0) && ky_ == 2) && !(ABL(6) && ky_ + kx_ + kk_ > 0)) DSR(fb[slot][nb], bb, (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
+            DSR(fb[slot][nb], bb, (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
 #define CV_LOAD(s, slot)                                                                                               \
             {                                                                                                          \
                 constexpr int tap_ = (s) / 2, kk_ = (s) % 2, ky_ = tap_ / 3, kx_ = tap_ % 3;                           \
@@ -417,7 +363,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             __builtin_amdgcn_sched_barrier(0);
 #define CV_STEP(s)                                                                                                     \
             {                                                                                                          \
-                if (!ABL(7)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* step s is in registers */        \
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* step s is in registers */                   \
                 __builtin_amdgcn_sched_barrier(0);                                                                     \
                 CV_ML_A(s, 0, 0, 0) CV_ML_A(s, 0, 1, 1) CV_ML_A(s, 0, 2, 2) CV_ML_A(s, 0, 3, 3)                        \
                 CV_ML_B(s, 1, 0, 0) CV_ML_B(s, 1, 1, 1) CV_ML_B(s, 1, 2, 2) CV_ML_B(s, 1, 3, 3)                        \
@@ -438,7 +384,6 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
 #undef CV_LOADB
 #undef CV_LOADA
 #undef DSR
-            STAMP(t2);
 
             // ---- epilogue, entirely in registers; a store covers two 256-byte runs (two chunks x 16 pixels) per wave ----
             // The residual / mask operands were requested before the K loop and have long returned, but vmcnt counts loads and
@@ -447,7 +392,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             // per bias+skip launch).  One explicit wait here (the builtin: hipcc's scoreboard then knows the queue is empty)
             // covers the operands; the stores after it are never waited for inside the tile.
             if (HAS_RES || MASK != MASK_NONE) __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) alone
-            if constexpr (RES_MFMA) {
+            if constexpr (HAS_RES) {
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
@@ -470,18 +415,15 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                         for (int j = 0; j < 4; ++j) { v[j] = acc[2 * k][nb][j]; v[4 + j] = acc[2 * k + 1][nb][j]; }
                         const unsigned wbits = k ? sbits.y : sbits.x;            // words wd = 16 k + 4 nb + jj
                         unsigned ow[4];
-                        if (ABL(4)) {
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_bf16(v[2 * jj], v[2 * jj + 1]);
-                        } else if (ACT == ACT_RELU && !HAS_RES && MASK == MASK_NONE) {
+                        if (ACT == ACT_RELU && !HAS_RES && MASK == MASK_NONE) {
                             // conv1 of a ResidualConv: round, then ReLU on the packed words (bf16 bit patterns order like int16
                             // for this purpose: negative and -0 -> +0), sign bit = "the stored half is non-zero"
 #pragma unroll
                             for (int jj = 0; jj < 4; ++jj) {
                                 ow[jj] = pk_max_i16(pk_bf16(v[2 * jj], v[2 * jj + 1]), 0u);
-                                if (!ABL(1)) sout[k] |= pk_min_u16(ow[jj], k11) << (4 * nb + jj);
+                                sout[k] |= pk_min_u16(ow[jj], k11) << (4 * nb + jj);
                             }
-                        } else if (ACT == ACT_LEAKY && !HAS_RES && MASK == MASK_NONE && !ABL(1)) {
+                        } else if (ACT == ACT_LEAKY && !HAS_RES && MASK == MASK_NONE) {
                             // conv_last.0: LeakyReLU = max(v, slope v) (0 < slope < 1), sign bits from the packed words as in the ReLU case
                             // (bit = "the stored half is positive", what sign_bits_c64_kernel computes from a stored activation)
 #pragma unroll
@@ -497,12 +439,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                         } else {
 #pragma unroll
                             for (int j = 0; j < 8; ++j) v[j] = p_act<ACT>(v[j], slope);
-                            if (HAS_RES && !(RES_MFMA && ACT == ACT_NONE)) {
-                                const unsigned rw[4] = {rr[k][nb].x, rr[k][nb].y, rr[k][nb].z, rr[k][nb].w};
-#pragma unroll
-                                for (int jj = 0; jj < 4; ++jj) { v[2 * jj] += bf_lo(rw[jj]); v[2 * jj + 1] += bf_hi(rw[jj]); }
-                            }
-                            if (ACT != ACT_NONE && !HAS_RES && !ABL(1)) {      // sign of the activation = sign of its argument (ReLU and LeakyReLU alike)
+                            if (ACT != ACT_NONE && !HAS_RES) {      // sign of the activation = sign of its argument (ReLU and LeakyReLU alike)
 #pragma unroll
                                 for (int j = 0; j < 8; ++j) sout[k] |= (v[j] > 0.f ? 1u : 0u) << (4 * nb + (j >> 1) + 16 * (j & 1));
                             }
@@ -525,32 +462,22 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                             for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_bf16(v[2 * jj], v[2 * jj + 1]);
                         }
                         const u32x4_t o = {ow[0], ow[1], ow[2], ow[3]};
-                        if (P_NT_STORE) __builtin_nontemporal_store(o, GP(u32x4_t, dst + k * 1024));
-                        else if (!ABL(5)) *GP(u32x4_t, dst + k * 1024) = o;
-                        else asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
+                        *GP(u32x4_t, dst + k * 1024) = o;
                     }
                 }
             }
             };
             if (full) epilogue(std::true_type{}); else epilogue(std::false_type{});
-            if (ACT != ACT_NONE && !HAS_RES && sout_z && !ABL(1)) sout_z[(long long)tile * 256 + w4 * 64 + lane] = u32x2_t{sout[0], sout[1]};
-            STAMP(t3);
+            if (ACT != ACT_NONE && !HAS_RES && sout_z) sout_z[(long long)tile * 256 + w4 * 64 + lane] = u32x2_t{sout[0], sout[1]};
             __syncthreads();                               // the producers' next tile has landed; everybody has finished reading `cur`
             cur ^= 1;
-            STAMP(t4);
-            STAMP_ADD(1, t0, t1); STAMP_ADD(2, t1, t2); STAMP_ADD(3, t2, t3); STAMP_ADD(4, t3, t4);
         }
     }
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     if (tid == 0 && blockIdx.y == 0 && blockIdx.x < 256) {
         g_clk[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime() - clk_t0;
         g_clk[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
     }
-#endif
-#ifdef VSR_STAMPS
-    st_sum[0] = stamp() - st_begin;
-    if (lane == 0 && blockIdx.y == 0 && blockIdx.x < 256)
-        for (int k = 0; k < 8; ++k) g_stamps[(blockIdx.x * 8 + wave) * 8 + k] = st_sum[k];
 #endif
 }
 
@@ -605,14 +532,9 @@ static int launch_persist(const ConvArgs& a, int num_cus, hipStream_t st) {
 
 }  // namespace
 
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
 extern "C" int vsr_debug_read_clk(unsigned long long* host_out) {      // [256 workgroups][cycles, 100 MHz ticks, -, -] of the last launch
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_clk), sizeof(unsigned long long) * 256 * 4) == hipSuccess ? 0 : -3;
-}
-#endif
-#ifdef VSR_STAMPS
-extern "C" int vsr_debug_read_stamps(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 256 * 8 * 8) == hipSuccess ? 0 : -3;
 }
 #endif
 

@@ -31,14 +31,9 @@ typedef __attribute__((ext_vector_type(2))) unsigned qu32x2_t;
 
 __device__ uint4 g_c7_zero_chunk[2];
 
-// Diagnostic build only (make ABL=<bits> ABLSRC=conv7x7_persist): results are WRONG by construction, only run time and the
-// in-kernel clock are read.  bit 0: the producers stream no weight rows after the prologue; bit 1: no fragment reads after a
-// kernel row's first step (bare MFMA loop); bit 2: no epilogue; bit 3: the producers load only the first tile.
-#ifdef VSR_ABL
+// The launch was taken apart with ablated builds of this file: DESIGN 4.3.  Clock build only (make CLOCK=1): the in-kernel clock.
+#ifdef VSR_CLOCK
 __device__ unsigned long long g_clk7[256 * 4];
-#define QABL(bit) ((VSR_ABL >> (bit)) & 1)
-#else
-#define QABL(bit) 0
 #endif
 
 __device__ __forceinline__ unsigned q_pk_bf16(float a, float b) {
@@ -127,7 +122,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
     const int role = __builtin_amdgcn_readfirstlane(wave >> 2);            // 0: MFMA + epilogue, 1: LDS-DMA producer
     const int w4 = wave & 3;
     const int l15 = lane & 15, q = lane >> 4;
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     unsigned long long clk_t0 = 0, clk_r0 = 0;
     if (tid == 0) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -228,10 +223,10 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
             int g = 0, gr2 = 2 % K::WROWS, sl2 = 2;             // gr2 = (g + 2) mod the period, sl2 = (g + 2) mod the ring
             for (int pass = 0; pass < my_passes; ++pass) {
                 const int hf = K::PASSES == 2 ? (pass & 1) : 0;
-                const bool next = pass + 1 < my_passes && !QABL(3);
+                const bool next = pass + 1 < my_passes;
                 if (pass + 1 < my_passes && (K::PASSES == 1 || hf == 1)) it.advance(walk.stride, ntx, nty);
                 for (int ky = 0; ky < 7; ++ky) {
-                    const bool more = g + 2 < nrows && !QABL(0);
+                    const bool more = g + 2 < nrows;
                     int inflight = 0;
                     if (more) { issue_wrow(gr2, sl2); inflight = my_row_pieces; }
                     if (next && ky < 5) inflight += issue_tile(it, K::PASSES == 2 ? (hf ^ 1) : 0, (pass + 1) & 1, ky * SL, ky * SL + SL);
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
             __builtin_amdgcn_s_barrier();
             for (int pass = 0; pass < my_passes; ++pass) {
                 inflight = 0;
-                if (pass + 2 < my_passes && !QABL(3)) {
+                if (pass + 2 < my_passes) {
                     it.advance(walk.stride, ntx, nty);
                     inflight = issue_tile(it, 0, (pass + 2) % K::NTB, 0, K::NPIECE_TW);
                 }
@@ -296,7 +291,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
 #define DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm))
         // fragment read l of step t_: l < 4: B block l (tile row (l >> 1) + ky, pixels 16 (l & 1) + kx ..), else A block l - 4
 #define QX_L(t_, l_)                                                                                                   \
-        if constexpr ((t_) < TS && (l_) < NL && !(QABL(1) && (t_) % K::KROW > 0)) {                                     \
+        if constexpr ((t_) < TS && (l_) < NL) {                                                                        \
             constexpr int ky_ = (t_) / K::KROW, s_ = (t_) % K::KROW;                                                   \
             if constexpr ((l_) < 4) { DSR(fb[(t_) % NF][(l_) & 3], bb, (ky_ + ((l_) >> 1)) * K::ROWPITCH + (((l_) & 1) * 16 + (CIN == 16 ? 2 * s_ : s_)) * 16); } \
             else { DSR(fa[(t_) % NF][((l_) - 4) & (NB - 1)], ab, (t_) * NB * 1024 + ((l_) - 4) * 1024); }               \
@@ -379,12 +374,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
             }
             if (K::PASSES == 1 || hf == 1) {
                 // ---- epilogue ----
-                if (QABL(2)) {
-#pragma unroll
-                    for (int mb = 0; mb < NB; ++mb)
-#pragma unroll
-                        for (int nb = 0; nb < 4; ++nb) asm volatile("" :: "v"(acc[mb][nb]));
-                } else if (EPI == EPI_NHWC) {
+                if (EPI == EPI_NHWC) {
                     const long long tbase = (long long)it.n * a.dst_nstride + pm_off(ty0, tx0, 0, a.W, a.CD);
                     const bool relu = a.act == ACT_RELU;
 #define QX_EPI(OKN)                                                                                                    \
@@ -445,7 +435,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
 #undef QX_L
 #undef DSR
     }
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     if (tid == 0 && blockIdx.x < 256) {
         g_clk7[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime() - clk_t0;
         g_clk7[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
@@ -471,7 +461,7 @@ int launch_c7(const ConvArgs& a, int cop, int num_cus, hipStream_t st) {
 
 }  // namespace
 
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
 extern "C" int vsr_debug_read_clk7(unsigned long long* host_out) {     // [256 workgroups][cycles, 100 MHz ticks, -, -] of the last launch
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_clk7), sizeof(unsigned long long) * 256 * 4) == hipSuccess ? 0 : -3;
 }

@@ -443,30 +443,22 @@ static_assert(DX_SLOTS % 64 == 0 && DY_SLOTS % 64 == 0, "whole DMA pieces");
 //     sets (48 registers) are live.  hipcc counts the lgkmcnt waits itself; sched_group_barrier pins the
 //     interleave "2 MFMAs, 2 reads".
 // ---------------------------------------------------------------------------------------------------
-// Diagnostic build only (make ABL=<bits> ABLSRC=wgrad_mfma): bit 0: the producers issue only the first tile's DMA (consumer-only
-// period); bit 1: the consumers skip the K loop (producer-only period).  Results are wrong by construction; only run time is read.
-// bit 2: the round-3 dY image (no slot shift of the odd chunks: bank conflicts on the A reads; results unchanged) for the A/B;
-// bit 3: nt instead of the default cache policy on the producers. LDS-DMA pieces (results unchanged).
+// The producer-only and consumer-only periods of this launch were measured with ablated builds of this file: DESIGN 4.2.
 // (r03: "B fragments for the ky = 0 groups only" measured -4 % with the DMA on, -7 % without: the K loop now shares an X row's
 // fragments across ky.)
-#ifdef VSR_ABL
-#define WABL(bit) ((VSR_ABL >> (bit)) & 1)
+#ifdef VSR_CLOCK
 __device__ unsigned long long g_wclk[256 * 4];          // [workgroup][cycles, 100 MHz ticks, consumer barrier-wait cycles, tiles] of the last launch
-#else
-#define WABL(bit) 0
 #endif
-#define DY_SHIFT (WABL(2) ? 0 : 1)      // slots by which the pixels of an odd chunk are shifted in the dY image
 // X and dY are streamed: every byte is read once per launch (halo rows twice, by a neighbour tile of the same XCD in flight at the same
 // time).  `nt` (aux = 2) on the LDS-DMA pieces: tools/bw_probe.hip reads 8 GiB at 6.4-7.0 TB/s with nt loads against 5.7-6.2 with plain
 // ones -- but this kernel does not care: 233.2 / 231.7 us (nt) against 230.1 / 234.3 (default) per 7-frame launch, the same 349 k cycles:
-// its producers are bound by the issue cost of their 80 pieces per tile, not by the policy.  Default policy kept; diagnostic bit 3 = nt.
-#define WG_DMA_AUX (WABL(3) ? 2 : 0)
+// its producers are bound by the issue cost of their 80 pieces per tile, not by the policy.  Default policy (aux = 0) kept.
 __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int role = __builtin_amdgcn_readfirstlane(wave >> 2);            // 0: MFMA consumer, 1: LDS-DMA producer
     const int w4 = __builtin_amdgcn_readfirstlane(wave & 3);
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     unsigned long long clk_t0 = 0, clk_r0 = 0, clk_bar = 0, clk_tiles = 0;
     if (tid == 0) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -514,7 +506,7 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
             } else {
                 const int idx = (piece - DX_PIECES) * 64 + lane;
                 const int row = idx / (8 * YS), rem = idx - row * (8 * YS);
-                const int c = rem / YS, tx = rem - c * YS - (c & 1) * DY_SHIFT;       // tx: the pixel of this slot
+                const int c = rem / YS, tx = rem - c * YS - (c & 1);                  // tx: the pixel of this slot
                 const int dx = (tx < 0 ? 0 : tx) * a.dy_step + a.dy_ox;
                 rel[i] = ((((row * a.dy_step) * pm_ws(a.Wy) + (dx >> 5)) * ycp + c) * 256 + (dx & 31) * 8) * 2;
                 if (tx < 0 || tx >= TW) padmask |= 1u << i;
@@ -568,14 +560,14 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
                         valid = vy >= 0 && vy < a.H && vx >= 0 && vx < a.W;
                     } else {
                         const int idx = (piece - DX_PIECES) * 64 + lane;
-                        const int row = idx / (8 * YS), rem = idx - row * (8 * YS), c = rem / YS, tx = rem - c * YS - (c & 1) * DY_SHIFT;
+                        const int row = idx / (8 * YS), rem = idx - row * (8 * YS), c = rem / YS, tx = rem - c * YS - (c & 1);
                         valid = ty0 + row < a.H && tx0 + tx < a.W;
                     }
                 }
                 if (!valid) src = zsrc;
                 char* dst = isx ? lxs + piece * 1024 : lxs + DXB + (piece - DX_PIECES) * 1024;
                 if (!pad) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                           (__attribute__((address_space(3))) void*)dst, 16, 0, WG_DMA_AUX);
+                                                           (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
             }
         };
         float bsum[8];
@@ -591,9 +583,9 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
             // the chip's LDS-DMA rate), and anything in front of the issue delays the whole transfer.  The bias-gradient partial
             // sums of the CURRENT dY tile follow, read by inline asm (hipcc would put a vmcnt(0) in front of a plain LDS read
             // while LDS-DMA is in flight; the DMA writes the OTHER buffer set).
-            const unsigned lyb = (unsigned)(cur * DSET + DXB + (pt & 7) * (YS * 16) + ((pt >> 3) + (pt & 1) * DY_SHIFT) * 16);
+            const unsigned lyb = (unsigned)(cur * DSET + DXB + (pt & 7) * (YS * 16) + ((pt >> 3) + (pt & 1)) * 16);
             advance();
-            if (it.T < walk.end && !WABL(0)) issue(cur ^ 1);
+            if (it.T < walk.end) issue(cur ^ 1);
             uint4 bq[8];
             asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:%9\n\tds_read_b128 %2, %8 offset:%10\n\tds_read_b128 %3, %8 offset:%11\n\t"
                          "ds_read_b128 %4, %8 offset:%12\n\tds_read_b128 %5, %8 offset:%13\n\tds_read_b128 %6, %8 offset:%14\n\tds_read_b128 %7, %8 offset:%15\n\t"
@@ -619,7 +611,7 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
         // 8 q + qq, channels 4 p4 .. 4 p4 + 3 of the fragment's 16; lane i of the group receives channel i of pixels
         // 8 q .. 8 q + 3 (second read, + 64 B: 8 q + 4 .. 8 q + 7) = the 16x16x32 operand's k = 8 q .. 8 q + 7.
         const int xoff = (ib * 4 + (p4 >> 1)) * (XS * 16) + (8 * q + qq) * 16 + (p4 & 1) * 8;
-        const int yoff = DXB + (cb * 4 + (p4 >> 1)) * (YS * 16) + (8 * q + qq + (p4 >> 1) * DY_SHIFT) * 16 + (p4 & 1) * 8;   // chunk parity = p4 >> 1
+        const int yoff = DXB + (cb * 4 + (p4 >> 1)) * (YS * 16) + (8 * q + qq + (p4 >> 1)) * 16 + (p4 & 1) * 8;   // chunk parity = p4 >> 1
         typedef union { s16x4_t s[2]; bf16x8_t b; } frag_u;
         f32x4_t acc[9][2][2];
 #pragma unroll
@@ -666,7 +658,6 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
 #define PC_GRP(R_, ky_, P0_, NV_) PC_PAIR(R_, ky_, 0, (P0_), NV_) PC_PAIR(R_, ky_, 1, (P0_) + 1, NV_) PC_PAIR(R_, ky_, 2, (P0_) + 2, NV_) \
                                   PC_PAIR(R_, ky_, 3, (P0_) + 3, NV_) PC_PAIR(R_, ky_, 4, (P0_) + 4, NV_) PC_PAIR(R_, ky_, 5, (P0_) + 5, NV_)
 #define PC_TOP { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-            if (!WABL(1)) {
             PC_TOP PC_GRP(0, 0, 0, 1)                                                     // R = 0: output row 0
             PC_TOP PC_GRP(1, 1, 0, 2) PC_GRP(1, 0, 6, 2)                                  // R = 1: rows 0 (ky 1), 1 (ky 0)
             PC_TOP PC_GRP(2, 2, 0, 3) PC_GRP(2, 1, 6, 3) PC_GRP(2, 0, 12, 3)
@@ -677,18 +668,17 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
             PC_TOP PC_GRP(7, 2, 0, 3) PC_GRP(7, 1, 6, 3) PC_GRP(7, 0, 12, 3)
             PC_TOP PC_GRP(8, 2, 0, 2) PC_GRP(8, 1, 6, 2)                                  // R = 8: rows 6 (ky 2), 7 (ky 1)
             PC_TOP PC_GRP(9, 2, 0, 1)                                                     // R = 9: row 7
-            }
 #undef PC_TOP
 #undef PC_GRP
 #undef PC_PAIR
 #undef PC_LDB
 #undef PC_LDA
 #undef PC_TRR
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
             unsigned long long b0; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(b0) :: "memory");
 #endif
             __syncthreads();                                   // next tile landed; everybody is done with `cur`
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
             unsigned long long b1; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(b1) :: "memory");
             clk_bar += b1 - b0; ++clk_tiles;
 #endif
@@ -715,7 +705,7 @@ __global__ __launch_bounds__(DNT, 2) void wgrad3x3_c64_pc_kernel(const WgradArgs
             slab[9 * 64 * 64 + tid] = s;
         }
     }
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
     if (tid == 0 && blockIdx.x < 256) {
         g_wclk[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime() - clk_t0;
         g_wclk[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
@@ -739,7 +729,7 @@ int launch_wgrad_pc(const WgradArgs& a0, int nwg, hipStream_t st) {      // nwg 
 
 }  // namespace
 
-#ifdef VSR_ABL
+#ifdef VSR_CLOCK
 extern "C" int vsr_debug_read_wclk(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wclk), sizeof(unsigned long long) * 256 * 4) == hipSuccess ? 0 : -3;
 }

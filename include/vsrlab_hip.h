@@ -311,6 +311,19 @@ int vsr_spectral_norm_backward(const float* dw, const float* w_orig, const float
 /* AdversarialLoss's core (core/losses.py:66-74): loss[0] = mean BCE-with-logits(x, target); dx (optional) = its gradient */
 int vsr_bce_with_logits(const float* x, float target, float* dx, float* loss, long long numel, void* stream);
 
+/* ---- PerceptualLoss (core/losses.py:8,29-64; csrc/perceptual_engine.hip) -------------------------------------------
+ * VGG19 features[:35] on sr and hr (n,3,h,w) fp32 planar, h, w >= 16; taps '2', '7', '16', '25' post-ReLU, '34' pre-ReLU.
+ * params: 32 device pointers, fp32 OIHW then bias, in state_dict order (vgg.vgg_layers.{0,2,5,...,34}.{weight,bias}).
+ * sums (device, fp64, n x 5) = per image and tap sum |f_k(sr) - f_k(hr)|: the caller scales and averages, so a batch may be
+ * split into chunks whose results add up to the batch's loss, bit for bit whatever the chunk size.
+ * need_grad = 1: dsr (n,3,h,w) fp32 planar = d/d sr of sum_k scales[k] * sum|f_k(sr) - f_k(hr)|, scales = 5 HOST floats
+ * (for the reference's loss: weight * LAYER_WEIGHTS[k] / numel of tap k over the whole batch).  No gradient into hr.
+ * need_grad = 0: dsr and scales must be NULL.                                                                      */
+typedef struct VsrPerceptualDesc { int n, h, w, dtype, need_grad; } VsrPerceptualDesc;
+size_t vsr_perceptual_workspace_bytes(const VsrPerceptualDesc* d);         /* 0: unsupported descriptor */
+int vsr_perceptual_loss(const VsrPerceptualDesc* d, const float* const* params, int nparams, const float* sr, const float* hr,
+                        const float* scales, double* sums, float* dsr, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VRT window attention (BASELINE config 5; csrc/window_attention.hip) ------------------------------------------
  * The core of WindowAttention.attention (vsr/models/VRT/modules/window_attention.py:140-162):
  *     out = softmax((q * scale) k^T [+ bias[head]] [+ mask[window % nW]]) v

@@ -1,6 +1,8 @@
 """BASELINE config 3 at size, for timing and rocprofv3: one GAN iteration = generator_step + backward + FusedAdam,
 discriminator_step + backward + FusedAdam (train_gan.py:35-58) on a (1,7,3,540,960) clip / seven 2160x3840 frames, bf16.
-    python tools/bench_gan.py [iters] [d|g|all]      d = discriminator step only, g = generator step only"""
+    python tools/bench_gan.py [iters] [d|g|all] [--perceptual]      d = discriminator step only, g = generator step only
+--perceptual: the generator step also runs PerceptualLoss(weight=1e-2) (conf/train/gan.yaml) with keyed random VGG19 weights,
+instead of dummy_loss (the default)."""
 import os
 import sys
 import time
@@ -12,8 +14,10 @@ os.environ.setdefault("VSRLAB_AMD_DTYPE", "bf16")
 
 
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    what = sys.argv[2] if len(sys.argv) > 2 else "all"
+    perceptual = "--perceptual" in sys.argv
+    argv = [a for a in sys.argv if a != "--perceptual"]
+    iters = int(argv[1]) if len(argv) > 1 else 3
+    what = argv[2] if len(argv) > 2 else "all"
     import importlib
     from vsrlab_amd.core.losses import AdversarialLoss, CharbonnierLoss
     from vsrlab_amd.optim import FusedAdam
@@ -32,12 +36,18 @@ def main():
     hr = torch.rand(1, 7, 3, 2160, 3840, device=dev)
     adv, crit = AdversarialLoss(), CharbonnierLoss()
     sr_fixed = torch.rand(1, 7, 3, 2160, 3840, device=dev)
+    ploss = dummy_loss
+    if perceptual:
+        from vsrlab_amd.core.losses import PerceptualLoss
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from perceptual_common import keyed_vgg_state_dict
+        ploss = PerceptualLoss(1e-2, vgg_weights=keyed_vgg_state_dict()).to(dev)
     for it in range(iters + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         sr = sr_fixed
         if what in ("all", "g"):
-            sr, loss_g, _, _ = generator_step(g, d, crit, dummy_loss, adv, lr, hr)
+            sr, loss_g, _, _ = generator_step(g, d, crit, ploss, adv, lr, hr)
             loss_g.backward()
             opt_g.step(max_grad_norm=1.0)
             opt_g.zero_grad()

@@ -877,6 +877,123 @@ def bce_with_logits_const(x: torch.Tensor, target: float) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------------- #
+# VGG19 perceptual loss (reference: core/losses.py:8,29-64)
+# --------------------------------------------------------------------------------------------- #
+PERCEPTUAL_LAYER_WEIGHTS = {'2': 0.1, '7': 0.1, '16': 0.8, '25': 0.9, '34': 1.0}
+# (features index, cout, cin) of the 16 convolutions of vgg19().features[:35]
+VGG19_CONVS = ((0, 64, 3), (2, 64, 64), (5, 128, 64), (7, 128, 128), (10, 256, 128), (12, 256, 256), (14, 256, 256), (16, 256, 256),
+               (19, 512, 256), (21, 512, 512), (23, 512, 512), (25, 512, 512), (28, 512, 512), (30, 512, 512), (32, 512, 512),
+               (34, 512, 512))
+_TAP_CHANNELS = (64, 128, 256, 512, 512)
+_TAP_LEVELS = (0, 1, 2, 3, 4)
+DEFAULT_PERCEPTUAL_WORKSPACE = 16 << 30
+
+
+def _perceptual_desc(n: int, h: int, w: int, dtype: int, need_grad: bool):
+    from ._lib import PerceptualDesc
+    return PerceptualDesc(int(n), int(h), int(w), int(dtype), int(bool(need_grad)))
+
+
+def perceptual_workspace_bytes(n: int, h: int, w: int, dtype: int = DT_F32, need_grad: bool = True) -> int:
+    """Device workspace of one ``vsr_perceptual_loss`` call on ``n`` images of h x w (0: unsupported).  Host arithmetic only."""
+    return int(_lib.load().vsr_perceptual_workspace_bytes(ctypes.byref(_perceptual_desc(n, h, w, dtype, need_grad))))
+
+
+def perceptual_chunk(n: int, h: int, w: int, dtype: int, need_grad: bool, max_workspace_bytes: Optional[int] = None) -> int:
+    """Images per call such that the workspace stays within the budget (at least 1: one image is the unit of work)."""
+    budget = DEFAULT_PERCEPTUAL_WORKSPACE if max_workspace_bytes is None else int(max_workspace_bytes)
+    one = perceptual_workspace_bytes(1, h, w, dtype, need_grad)
+    per = perceptual_workspace_bytes(2, h, w, dtype, need_grad) - one
+    if one == 0 or one > budget:
+        return 1
+    return int(max(1, min(n, 1 + (budget - one) // max(per, 1))))
+
+
+def _tap_numels(n: int, h: int, w: int):
+    out = []
+    for c, lv in zip(_TAP_CHANNELS, _TAP_LEVELS):
+        hh, ww = h, w
+        for _ in range(lv):
+            hh, ww = hh // 2, ww // 2
+        out.append(n * c * hh * ww)
+    return out
+
+
+class _PerceptualFn(torch.autograd.Function):
+    """loss = weight * sum_k LAYER_WEIGHTS[k] * mean|f_k(sr) - f_k(hr)|.  d loss / d sr is computed during the forward (one
+    engine call per chunk of images) and is all the backward keeps; hr gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, dtype, weight, chunk, need_grad, terms_out, *params):
+        lib = _lib.load()
+        h, w = hr.shape[-2], hr.shape[-1]
+        sr4, hr4 = _f32c(sr).reshape(-1, 3, h, w), _f32c(hr).reshape(-1, 3, h, w)
+        n = sr4.shape[0]
+        p32 = [_f32c(p) for p in params]
+        lw = list(PERCEPTUAL_LAYER_WEIGHTS.values())
+        numels = _tap_numels(n, h, w)
+        scales = (ctypes.c_float * 5)(*[float(weight) * lw[k] / numels[k] for k in range(5)])
+        dev = sr4.device
+        sums = torch.empty((n, 5), dtype=torch.float64, device=dev)
+        dsr = torch.empty_like(sr4) if need_grad else None
+        nbytes = perceptual_workspace_bytes(min(chunk, n), h, w, dtype, need_grad)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        parr = _ptr_array(p32)
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            desc = _perceptual_desc(m, h, w, dtype, need_grad)
+            _lib.check(lib.vsr_perceptual_loss(ctypes.byref(desc), parr, 32, _ptr(sr4[i:i + m]), _ptr(hr4[i:i + m]),
+                                               scales if need_grad else None, _ptr(sums[i:i + m]),
+                                               _ptr(dsr[i:i + m] if need_grad else None), _ptr(ws), nbytes, _stream()), "perceptual_loss")
+        del ws
+        coef = torch.tensor([float(weight) * lw[k] / numels[k] for k in range(5)], dtype=torch.float64, device=dev)
+        terms = sums.sum(0) * coef
+        if terms_out is not None:
+            terms_out.append(terms)
+        ctx.dsr = dsr.reshape(sr.shape) if need_grad else None
+        ctx.backward_done = False
+        ctx.sr_dtype = sr.dtype
+        return terms.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError("vsrlab_amd: perceptual_loss has no double backward (create_graph=True is not supported)")
+        if ctx.backward_done:
+            raise RuntimeError("vsrlab_amd: trying to backward through the perceptual loss a second time")
+        if ctx.dsr is None:
+            raise RuntimeError("vsrlab_amd: backward through a perceptual loss that ran without a gradient")
+        dsr, ctx.dsr, ctx.backward_done = ctx.dsr, None, True
+        return (g * dsr).to(ctx.sr_dtype), None, None, None, None, None, None, *([None] * 32)
+
+
+def perceptual_loss(sr: torch.Tensor, hr: torch.Tensor, params: Sequence[torch.Tensor], weight: float = 1.0,
+                    compute_dtype: Optional[str] = None, max_workspace_bytes: Optional[int] = None,
+                    return_terms: bool = False):
+    """PerceptualLoss.forward (core/losses.py:47-64) on the HIP path.  ``sr``, ``hr``: (..., 3, h, w), h, w >= 16.  ``params``: the
+    32 tensors of vgg19().features[:35] (weight, bias of features.{0,2,5,...,34}).  The batch runs in chunks whose workspace
+    stays within ``max_workspace_bytes`` (default 16 GiB).  ``return_terms``: also return the five weighted tap terms (fp64)."""
+    if sr.shape != hr.shape or sr.dim() < 3 or sr.shape[-3] != 3:
+        raise ValueError(f"perceptual_loss: sr and hr must have one shape (..., 3, h, w); got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    h, w = hr.shape[-2], hr.shape[-1]
+    if h < 16 or w < 16 or sr.numel() == 0:
+        raise ValueError(f"perceptual_loss: frames must be at least 16 x 16 (four 2x2 max-pools), got {h} x {w}")
+    if len(params) != 32:
+        raise ValueError(f"perceptual_loss: expected the 32 weight / bias tensors of vgg19().features[:35], got {len(params)}")
+    for (idx, co, ci), wt, b in zip(VGG19_CONVS, params[0::2], params[1::2]):
+        if tuple(wt.shape) != (co, ci, 3, 3) or tuple(b.shape) != (co,):
+            raise ValueError(f"perceptual_loss: features.{idx} must be Conv2d({ci}, {co}, 3): got {tuple(wt.shape)} / {tuple(b.shape)}")
+    _require_gpu(sr, hr, *params)
+    dtype = resolve_dtype(compute_dtype)
+    n = sr.numel() // (3 * h * w)
+    need_grad = torch.is_grad_enabled() and sr.requires_grad
+    chunk = perceptual_chunk(n, h, w, dtype, need_grad, max_workspace_bytes)
+    terms = [] if return_terms else None
+    loss = _PerceptualFn.apply(sr, hr.detach(), dtype, float(weight), chunk, need_grad, terms, *params)
+    return (loss, terms[0]) if return_terms else loss
+
+
+# --------------------------------------------------------------------------------------------- #
 # VRT window attention core (reference: vsr/models/VRT/modules/window_attention.py:116-162)
 # --------------------------------------------------------------------------------------------- #
 _MASK_BITS = {}

@@ -5,9 +5,9 @@ signatures and return values, and the same ``autocast`` regions (train_gan.py:38
 pick the bf16 build (``functional.resolve_dtype``), so a caller that uses these functions as drop-ins gets the
 documented bf16 path without setting ``compute_dtype`` / ``$VSRLAB_AMD_DTYPE`` (the reference's fp16 autocast maps to
 bf16 storage / fp32 accumulate on MI355X; an enclosing ``torch.autocast(enabled=False)`` is NOT overridden by the
-reference either).  The perceptual loss (VGG19 pretrained, core/losses.py:34) needs downloaded weights
-and is out of scope: pass ``dummy_loss``, which is what the reference uses for ``perceptual_loss: null``
-(train_gan.py:98)."""
+reference either).  ``perceptual_loss`` is ``core.losses.PerceptualLoss`` (VGG19, the reference's conf/train/gan.yaml,
+weight 1e-2; HIP engine, weights from torchvision's local cache or a file / state dict, never downloaded) or ``dummy_loss``,
+which is what the reference uses for ``perceptual_loss: null`` (train_gan.py:98)."""
 import torch
 
 from .core.utils import compute_loss

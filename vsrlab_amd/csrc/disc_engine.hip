@@ -17,21 +17,12 @@
 // The pre-residual activations a4, a5, a6 are kept besides the sums: LeakyReLU' needs the sign of the activation, which
 // the sum with the skip no longer has.
 #include <vector>
-#include "kernels.h"
-#include "../../include/vsrlab_hip.h"
+#include "host.h"
 
 namespace {
 
 constexpr float SLOPE = 0.2f;      // unet-discriminator.py:19
 constexpr int C = 64;
-
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
-};
-inline size_t esize(int dtype) { return dtype == VSR_BF16 ? 2 : 4; }
-
-#define CK(expr) do { int _s = (expr); if (_s != VSR_OK) return _s; } while (0)
 
 struct DPlan {
     int n, h, w, dtype; size_t es;
@@ -50,7 +41,7 @@ struct DPlan {
     int build(const VsrDiscDesc& d, int need_backward) {
         n = d.n; h = d.h; w = d.w; dtype = d.dtype;
         if (d.mid_ch != C || n < 1 || h < 8 || w < 8 || (h & 7) || (w & 7)) return VSR_ERR_UNSUPPORTED;
-        if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
+        if (bad_dtype(dtype)) return VSR_ERR_BADARG;
         es = esize(dtype);
         Bump b;
         const size_t w64 = (size_t)9 * C * C * es;
@@ -77,9 +68,8 @@ struct DPlan {
             du4 = b.take(pm1(h / 2, w / 2, 256)); ds4 = b.take(pm1(h / 4, w / 4, 256)); dc4 = b.take(pm1(h / 4, w / 4, 256));
             du3 = b.take(pm1(h / 4, w / 4, 512)); dc3 = b.take(pm1(h / 8, w / 8, 512)); dc2 = b.take(pm1(h / 4, w / 4, 256));
             dc1 = b.take(pm1(h / 2, w / 2, 128)); dc0 = b.take(pm1(h, w, 64));
-            int cp, xp, stride;
-            vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-            slab = b.take((size_t)(VSR_WGRAD_NWG > VSR_WGRAD_MAX_PAIR_SLABS ? VSR_WGRAD_NWG : VSR_WGRAD_MAX_PAIR_SLABS) * stride * 4);
+            // partials of 3x3 64 -> 64 blocks: one per workgroup (wgrad_slab_bytes()) or per pair and pixel part of a pair-batched launch
+            slab = b.take((size_t)(VSR_WGRAD_NWG > VSR_WGRAD_MAX_PAIR_SLABS ? VSR_WGRAD_NWG : VSR_WGRAD_MAX_PAIR_SLABS) * wgrad_slab_stride3() * 4);
         }
         total = b.off;
         return VSR_OK;
@@ -104,10 +94,7 @@ struct DCtx {
     const float* fat(size_t o) const { return reinterpret_cast<const float*>(ws + o); }
 
     ConvArgs base(int H, int W) const {
-        ConvArgs a = {};
-        a.in_step = 1; a.Hs = H; a.Ws = W; a.N = p.n; a.H = H; a.W = W; a.nz = 1;
-        a.out_step = 1; a.Hd = H; a.Wd = W; a.CD = C; a.cout_real = C; a.dst_nstride = pm_image_elems(H, W, C);
-        a.src_nstride[0] = pm_image_elems(H, W, C);
+        ConvArgs a = conv_args(p.n, H, W, C);
         a.leaky_slope = SLOPE;
         return a;
     }
@@ -135,18 +122,11 @@ struct DCtx {
         a.x[0] = x; a.x_step = x_step; a.x_oy = view >= 0 ? (view >> 1) : 0; a.x_ox = view >= 0 ? (view & 1) : 0;
         a.Hx = Hx; a.Wx = Wx; a.x_nstride = pm_image_elems(Hx, Wx, xC); a.x_ctotal = xC; a.x_coff = x_slice * 8;
         a.dy[0] = dy; a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, dyC); a.dy_ctotal = dyC; a.dy_coff = dy_slice * 8;
-        int cp, xp, stride;
-        vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-        a.slab = (float*)at(p.slab); a.slab_stride = stride;
-        const int tiles = p.n * cdiv(H, 8) * cdiv(W, 32);
-        int nwg = tiles < VSR_WGRAD_NWG ? tiles : VSR_WGRAD_NWG;
-        if (nwg > 1) nwg &= ~1;
+        const WgradShape shape = {3, 64, false, 64, false};
+        if (view < 0) return wgrad_run(st, dtype, (float*)at(p.slab), a, shape, {64, 64, gw + (size_t)co0 * cin_total * 9, cin_total, ci0, 1, 0, nullptr, 1});
         int nslabs = 0;
-        CK(vsr_launch_wgrad(dtype, 3, 64, 0, 64, 0, a, nwg, &nslabs, st));
-        if (view < 0)
-            return vsr_launch_wgrad_reduce((const float*)at(p.slab), nslabs, 3, 64, 64, 64, 64, gw + (size_t)co0 * cin_total * 9, cin_total, ci0, 1, 0,
-                                           nullptr, 1, st);
-        return vsr_launch_wgrad_reduce_s2((const float*)at(p.slab), nslabs, stride, gw, cin_total, co0, ci0, view, st);
+        CK(wgrad_launch(st, dtype, (float*)at(p.slab), a, shape, true, &nslabs));
+        return vsr_launch_wgrad_reduce_s2((const float*)at(p.slab), nslabs, a.slab_stride, gw, cin_total, co0, ci0, view, st);
     }
     // the whole weight gradient of a wide layer: x (xC channels; views == 4: the four parity views of a 4x4 stride-2 conv's input),
     // dy (dyC channels).  bf16: every (view, cout block, cin slice) pair in one launch + one reduction; fp32: pair by pair.
@@ -157,9 +137,7 @@ struct DCtx {
             a.N = p.n; a.H = H; a.W = W; a.nseg = 1;
             a.x[0] = x; a.x_step = x_step; a.Hx = Hx; a.Wx = Wx; a.x_nstride = pm_image_elems(Hx, Wx, xC); a.x_ctotal = xC;
             a.dy[0] = dy; a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, dyC); a.dy_ctotal = dyC;
-            int cp, xp, stride;
-            vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-            a.slab = (float*)at(p.slab); a.slab_stride = stride;
+            a.slab = (float*)at(p.slab); a.slab_stride = wgrad_slab_stride3();
             const int tiles = p.n * cdiv(H, 8) * cdiv(W, 32);
             int ksplit = ((512 / npairs) + 7) & ~7;                       // ~512 workgroups per launch
             if (ksplit < 8) ksplit = 8;

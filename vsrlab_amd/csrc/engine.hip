@@ -7,21 +7,9 @@
 // of the clip is retained, so each layer's weight gradient is ONE split-K launch over all t frames
 // (see wgrad_mfma.hip) instead of t launches + t reductions.
 #include <vector>
-#include "kernels.h"
-#include "../../include/vsrlab_hip.h"
+#include "host.h"
 
 namespace {
-
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    }
-};
-
-inline size_t esize(int dtype) { return dtype == VSR_BF16 ? 2 : 4; }
 
 constexpr int C = 64;           // mid channels of the HIP path (the narrow entries run 16 / 32: Plan::C shadows this in the engine)
 constexpr int NSPY = 5;         // convs per SPyNet level
@@ -32,18 +20,18 @@ const int SPY_CD[NSPY] = {32, 64, 32, 16, 0};     // channels per pixel of each 
 const int SPY_DK[NSPY] = {32, 64, 32, 16, 16}, SPY_DROWS[NSPY] = {32, 32, 64, 32, 32};
 
 struct SpyPlan {
-    int P, F, h, w, hu, wu;
-    size_t pyr[6];          // planar fp32 normalised frames, level 0 = coarsest
-    size_t x16, b32a, b64, b32b, b16;   // pixel-major T at the finest level size
-    size_t flow_a, flow_b, flow_up;     // planar fp32 [P][2][hu][wu]
-    size_t wpack[6][NSPY], bias[6][NSPY];
+    int P = 0, F = 0, h = 0, w = 0, hu = 0, wu = 0;
+    size_t pyr[6] = {};          // planar fp32 normalised frames, level 0 = coarsest
+    size_t x16 = 0, b32a = 0, b64 = 0, b32b = 0, b16 = 0;   // pixel-major T at the finest level size
+    size_t flow_a = 0, flow_b = 0, flow_up = 0;     // planar fp32 [P][2][hu][wu]
+    size_t wpack[6][NSPY] = {}, bias[6][NSPY] = {};
     // train_flow (need_backward = 2): per-level saved activations, dgrad weights and backward scratch
     bool save = false;
-    size_t sx[6][NSPY];                 // inputs of the 5 convs of each level: x16, b32a, b64, b32b, b16
-    size_t sfup[6], sres[6];            // planar fp32 flow_up and residue (= ReLU(conv5)) per level
-    size_t wpackd[6][NSPY];
-    size_t gA, gB, dres, dfa, dfb;
-    size_t dpyr[6];                     // gradient of the normalised pyramid (input-frame gradient)
+    size_t sx[6][NSPY] = {};                 // inputs of the 5 convs of each level: x16, b32a, b64, b32b, b16
+    size_t sfup[6] = {}, sres[6] = {};            // planar fp32 flow_up and residue (= ReLU(conv5)) per level
+    size_t wpackd[6][NSPY] = {};
+    size_t gA = 0, gB = 0, dres = 0, dfa = 0, dfb = 0;
+    size_t dpyr[6] = {};                     // gradient of the normalised pyramid (input-frame gradient)
     void plan_save(Bump& b, int dtype) {
         save = true;
         const size_t es = esize(dtype);
@@ -84,33 +72,33 @@ struct SpyPlan {
 };
 
 struct Plan {
-    VsrBasicVSRDesc d;
+    VsrBasicVSRDesc d = {};
     // mid channels: 64 (the whole-path entries: chains, persistent kernels, sign bits, phase planes) or 16 / 32 (the narrow entries:
     // one generic-kernel launch per layer, ReLU / LeakyReLU masks of the data gradients from the stored activations); CO: the conv
     // template's output rows for C outputs (C = 16 runs on the 32-row template with cout_real = 16)
     int C = 64, CO = 64;
     bool sb = false;             // sign bits of the masked data gradients are kept (bf16 training at C = 64)
-    bool bwd, flowgrad;          // flowgrad: train_flow (basicvsr.py:25-28), SPyNet is differentiated too
-    bool diet;                   // VsrBasicVSRDesc.arena_mode = 1 (training only): see vsrlab_hip.h
-    int rb, n, t, h, w, dtype;
-    int scale, ups;              // upscale (2 or 4, basicvsr.py:12-23) and its PixelShufflePack count scale / 2
-    bool unsh;                   // the gradients INTO the pixel-shuffle layers (G_U1, G_U0) are kept phase-separated (ConvArgs::unshuffle)
-    size_t es;
-    size_t px1;                 // elements of one blocked (n,h,w,64) tensor
-    size_t s_elems;             // elements of the plain 64-bit fixed-point warp-scatter accumulator (n,h,w,64)
+    bool bwd = false, flowgrad = false;          // flowgrad: train_flow (basicvsr.py:25-28), SPyNet is differentiated too
+    bool diet = false;           // VsrBasicVSRDesc.arena_mode = 1 (training only): see vsrlab_hip.h
+    int rb = 0, n = 0, t = 0, h = 0, w = 0, dtype = VSR_F32;
+    int scale = 4, ups = 2;      // upscale (2 or 4, basicvsr.py:12-23) and its PixelShufflePack count scale / 2
+    bool unsh = false;           // the gradients INTO the pixel-shuffle layers (G_U1, G_U0) are kept phase-separated (ConvArgs::unshuffle)
+    size_t es = 4;
+    size_t px1 = 0;             // elements of one blocked (n,h,w,64) tensor
+    size_t s_elems = 0;         // elements of the plain 64-bit fixed-point warp-scatter accumulator (n,h,w,64)
     // packed weights / biases
-    size_t stem_w[2], stem_wd[2], stem_b[2];
+    size_t stem_w[2] = {}, stem_wd[2] = {}, stem_b[2] = {};
     std::vector<size_t> blk_w[2], blk_wd[2], blk_b[2];     // [2*rb]: conv1, conv2 alternating
-    size_t point_w, point_wd, point_b;
-    size_t up_w[2], up_wd[2], up_b[2];
-    size_t last0_w, last0_wd, last0_b, last2_w, last2_wd, last2_b;
+    size_t point_w = 0, point_wd = 0, point_b = 0;
+    size_t up_w[2] = {}, up_wd[2] = {}, up_b[2] = {};
+    size_t last0_w = 0, last0_wd = 0, last0_b = 0, last2_w = 0, last2_wd = 0, last2_b = 0;
     SpyPlan spy;
-    size_t flows;               // fp32 planar [2*n*(t-1)][2][h][w]: first half backward, second half forward
+    size_t flows = 0;               // fp32 planar [2*n*(t-1)][2][h][w]: first half backward, second half forward
     // trunk activations: [dir][frame]
     std::vector<size_t> Wp[2], X[2], A[2];      // X: (rb+1) per frame, A: rb per frame (saved mode)
     std::vector<size_t> SB[2];                  // sign bits of A (bf16 build): rb per frame, 8 bytes per lane and 8x32 tile
     std::vector<size_t> feat[2];                // = X[rb]
-    size_t scratchA[2], scratchW[2];            // inference mode, per direction (the directions run concurrently)
+    size_t scratchA[2] = {}, scratchW[2] = {};            // inference mode, per direction (the directions run concurrently)
     // reconstruction
     std::vector<size_t> Pt, U0, U1, C0;
     std::vector<size_t> SBC0;                   // sign bits of C0 = LeakyReLU(conv_last.0) per frame (bf16 build, training)
@@ -119,19 +107,19 @@ struct Plan {
     // backward
     std::vector<size_t> G0[2], G1[2], DX[2];    // G1: rb per frame, DX: (rb+1) per frame (DX[0] unused -> G0)
     std::vector<size_t> dFeatB, dFF;            // per frame: d outputs[i], d feat_prop(i) from the reconstruction
-    size_t S[2], dWp[2], slab[2];               // per direction / stream
-    size_t far_cnt;                             // [2][t] ints: far-source counters of the gather-form warp backward
+    size_t S[2] = {}, dWp[2] = {}, slab[2] = {};               // per direction / stream
+    size_t far_cnt = 0;                             // [2][t] ints: far-source counters of the gather-form warp backward
     size_t chain_sync[2] = {0, 0};              // counters of the trunk chain launches (0: chains not planned)
     bool chains = true;                         // VSRLAB_AMD_CHAIN, read ONCE per engine call (build()): 0 one launch per layer, else chains
-    size_t G_C0, G_U1, G_U0, G_P;
+    size_t G_C0 = 0, G_U1 = 0, G_U0 = 0, G_P = 0;
     // r04 (full arena, bf16): the gradients into the two pixel-shuffle layers and into the 1x1 fuse conv are kept PER FRAME (+9.8 GB per
     // clip at config 2), so that those layers' weight gradients are all-frames launches like the trunks' (28 + 28 + 14 one-frame launches
     // of 50-140 us each per step before: a one-frame launch at LR size is mostly prologue, slab write and first-tile latency)
     bool hrdef = false;
     std::vector<size_t> GU1f, GU0f, GPf;
-    size_t dflows;              // fp32 planar, layout of `flows`: gradient w.r.t. the flows (train_flow / input gradient)
-    size_t stem_wd_lr[2];       // data-gradient weights of the stems' 3 LR input channels (input gradient)
-    size_t total;
+    size_t dflows = 0;              // fp32 planar, layout of `flows`: gradient w.r.t. the flows (train_flow / input gradient)
+    size_t stem_wd_lr[2] = {};       // data-gradient weights of the stems' 3 LR input channels (input gradient)
+    size_t total = 0;
 
     size_t xoff(int dir, int i, int b) const { return X[dir][(size_t)i * (rb + 1) + b]; }
     size_t aoff(int dir, int i, int b) const { return A[dir][(size_t)i * rb + b]; }
@@ -252,9 +240,7 @@ struct Plan {
                     GU1f[i] = ups == 2 ? b.take(gu1) : GU0f[i];
                     GPf[i] = b.take(a1);
                 }
-            int cp, xp, stride;
-            vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-            for (int k = 0; k < 2; ++k) slab[k] = b.take((size_t)VSR_WGRAD_NWG * stride * 4);
+            for (int k = 0; k < 2; ++k) slab[k] = b.take(wgrad_slab_bytes());
         }
         // the trunk chains' work / row counters (conv3x3_chain.hip), one block per direction (= per stream)
         for (int dir = 0; dir < 2; ++dir) chain_sync[dir] = sb ? b.take(vsr_chain_sync_bytes(VSR_CHAIN_MAX_LAYERS, n, h, w)) : 0;
@@ -272,53 +258,67 @@ struct Plan {
     }
 };
 
-#define CK(expr) do { int _s = (expr); if (_s != VSR_OK) return _s; } while (0)
-
+// What every launch recipe needs: the stream, the compute dtype, the mid-channel width and (backward) this stream's weight-gradient
+// slab buffer.  The engines address their arena through at() / fat(); the per-op entries (ws = null) run the same recipes on the
+// caller's buffers.
 struct Ctx {
-    const Plan& p;
     char* ws;
     hipStream_t st;
     int dtype;
-    int lane;                   // 0: the caller's stream, 1: the helper stream (selects per-stream scratch)
+    // mid channels: 64 (persistent kernels, sign bits, phase planes) or 16 / 32 (one generic-kernel launch per layer); CO: the conv
+    // template's output rows for C outputs (C = 16 runs on the 32-row template with cout_real = 16)
+    int C, CO;
+    size_t es;
+    float* slab;                // wgrad_slab_bytes() for the weight-gradient partials of this stream (null: no backward)
     mutable std::vector<VsrPackDesc>* batch = nullptr;      // while set, pack() collects descriptors for ONE multi-tensor launch
+    Ctx(char* ws_, hipStream_t st_, int dtype_, int C_ = 64, float* slab_ = nullptr)
+        : ws(ws_), st(st_), dtype(dtype_), C(C_), CO(C_ < 32 ? 32 : C_), es(esize(dtype_)), slab(slab_) {}
     void* at(size_t off) const { return ws + off; }
     const float* fat(size_t off) const { return reinterpret_cast<const float*>(ws + off); }
 
-    ConvArgs base(int N, int H, int W) const {
-        const int C = p.C;
-        ConvArgs a = {};
-        a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1;
-        a.out_step = 1; a.Hd = H; a.Wd = W; a.CD = C; a.cout_real = C; a.dst_nstride = pm_image_elems(H, W, C);
-        for (int s = 0; s < VSR_MAX_SRC; ++s) a.src_nstride[s] = pm_image_elems(H, W, C);
-        return a;
-    }
     // the destination of `a` (an N x H x W x 64 image, H and W even) as four phase planes of N x H/2 x W/2 x 64 (ConvArgs::unshuffle)
-    static long long plane_elems(int N, int H, int W) { return (long long)N * pm_image_elems(H / 2, W / 2, C); }
+    static long long plane_elems(int N, int H, int W) { return (long long)N * pm_image_elems(H / 2, W / 2, 64); }
     static void set_unshuffle(ConvArgs& a, int N, int H, int W) {
-        a.unshuffle = 1; a.unshuffle_plane = plane_elems(N, H, W); a.dst_nstride = pm_image_elems(H / 2, W / 2, C);
+        a.unshuffle = 1; a.unshuffle_plane = plane_elems(N, H, W); a.dst_nstride = pm_image_elems(H / 2, W / 2, 64);
     }
-    // y = act(conv3x3(x) + bias) (+res) (*mask(aux)) -- C -> C at one resolution (C = p.C; sign bits at C = 64 only)
-    int conv64(const void* x, size_t wpack, const float* bias, void* y, int act, const void* res, const void* aux, int mask,
-               int N, int H, int W, void* sign_out = nullptr, const void* sign_bits = nullptr, bool unshuffle = false) const {
-        ConvArgs a = base(N, H, W);
-        a.src[0] = x; a.wpack = at(wpack); a.bias = bias; a.dst[0] = y; a.act = act; a.res[0] = res; a.aux[0] = aux; a.mask_mode = mask;
+    // y = act(conv(x) + bias) (+res) (*mask(aux)) -- C -> C, 3x3 or 1x1, at one resolution (bf16 3x3 at C = 64: the persistent
+    // kernel; sign bits and phase-separated outputs exist there only)
+    int conv(int ks, const void* x, const void* wpack, const float* bias, void* y, int act, const void* res, const void* aux, int mask,
+             int N, int H, int W, void* sign_out = nullptr, const void* sign_bits = nullptr, bool unshuffle = false, float slope = 0.f) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.src[0] = x; a.wpack = wpack; a.bias = bias; a.dst[0] = y; a.act = act; a.leaky_slope = slope; a.res[0] = res; a.aux[0] = aux; a.mask_mode = mask;
         a.sign_out[0] = sign_out; a.sign_bits[0] = sign_bits;
         if (unshuffle) set_unshuffle(a, N, H, W);
-        if (p.C != 64) return vsr_launch_conv(dtype, 3, 1, p.C, p.C, 0, p.CO, EPI_NHWC, a, st);
-        const int rc = vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+        const int rc = vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st);
         // VSRLAB_AMD_GENERIC_CONV=1 (A/B switch): the generic kernel does not write sign bits, but later launches (hr_tail.hip's
         // conv_last.2 data gradient, the masked data gradients) read them -- r04: the switch gave wrong gradients since round 2
         if (rc == VSR_OK && sign_out && dtype == VSR_BF16 && vsr_env().generic_conv) return vsr_launch_sign_bits_c64(y, sign_out, N, H, W, st);
         return rc;
     }
+    // C -> 3 planar fp32 (+ pres): the stems' LR-channel gradient, the pre-clean out conv
+    int conv_planar3(const void* x, const void* wpack, const float* bias, float* y, long long y_nstride, const float* pres, int N, int H, int W) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.src[0] = x; a.wpack = wpack; a.bias = bias; a.cout_real = 3; a.dst[0] = y; a.dst_nstride = y_nstride; a.pres = pres;
+        return vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st);
+    }
+
+    // ---- PixelShufflePack (upsampling.py:4-12) ----
+    // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c+2i+j, y, x]  => sub-conv z uses rows 4c+z and bias entries 4c+z
+    int pack_ps(const float* w, void* dst, int mode) const {
+        for (int z = 0; z < 4; ++z) CK(pack(w, (char*)dst + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, mode));
+        return VSR_OK;
+    }
+    int pack_ps_bias(const float* b, float* dst) const {
+        for (int z = 0; z < 4; ++z) CK(pack_bias(b, dst + z * C, C, 4, z));
+        return VSR_OK;
+    }
     // conv3x3 C->4C + PixelShuffle(2): x (N,H,W,C) -> y (N,2H,2W,C)   (upsampling.py:10-12)
-    int conv_ps(const void* x, size_t wpack, const float* bias4, void* y, int N, int H, int W) const {
-        const int C = p.C;
-        ConvArgs a = base(N, H, W);
-        a.src[0] = x; a.wpack = at(wpack); a.w_zstride = 9 * p.CO * C; a.bias = bias4; a.bias_zstride = C; a.nz = 4;
+    int conv_ps(const void* x, const void* wpack, const float* bias4, void* y, int N, int H, int W, int act = ACT_NONE, float slope = 0.f) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.src[0] = x; a.wpack = wpack; a.w_zstride = 9 * CO * C; a.bias = bias4; a.bias_zstride = C; a.nz = 4; a.act = act; a.leaky_slope = slope;
         a.out_step = 2; a.Hd = 2 * H; a.Wd = 2 * W; a.dst_nstride = pm_image_elems(2 * H, 2 * W, C);
         for (int z = 0; z < 4; ++z) { a.dst[z] = y; a.out_oy[z] = z >> 1; a.out_ox[z] = z & 1; }
-        return vsr_launch_conv(dtype, 3, 1, C, C, 0, p.CO, EPI_NHWC, a, st);
+        return vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st);
     }
     // data gradient of the above: dy (N,2H,2W,64) -> dx (N,H,W,64) (* mask(aux)) = sum over the 4 pixel-shuffle
     // phases z of a transposed 3x3 64->64 conv of dy's phase z.  bf16: four launches of the persistent kernel (the
@@ -329,19 +329,18 @@ struct Ctx {
     // contiguous tensor instead of every second pixel of every second row of the 2H x 2W image (r04: the strided form fetched every
     // line of dy twice per data gradient and again twice per weight gradient); dx_planes: write dx phase-separated in turn.
     // C < 64: the one 4-source launch in both dtypes (the persistent kernel is 64-channel).
-    int conv_ps_dgrad(const void* dy, size_t wpackd, void* dx, const void* aux, int mask, int N, int H, int W, const void* sign_bits = nullptr,
+    int conv_ps_dgrad(const void* dy, const void* wpackd, void* dx, const void* aux, int mask, int N, int H, int W, const void* sign_bits = nullptr,
                       bool dy_planes = false, bool dx_planes = false) const {
-        const int C = p.C;
         if (dtype == VSR_BF16 && C == 64) {
             for (int z = 0; z < 4; ++z) {
-                ConvArgs a = base(N, H, W);
+                ConvArgs a = conv_args(N, H, W, C);
                 if (dy_planes) {
-                    a.src[0] = (const char*)dy + (size_t)z * plane_elems(N, 2 * H, 2 * W) * p.es;      // plane z: N x H x W, stride 1 (base() set it up)
+                    a.src[0] = (const char*)dy + (size_t)z * plane_elems(N, 2 * H, 2 * W) * es;      // plane z: N x H x W, stride 1 (conv_args() set it up)
                 } else {
                     a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
                     a.src[0] = dy; a.src_oy[0] = z >> 1; a.src_ox[0] = z & 1; a.src_nstride[0] = pm_image_elems(2 * H, 2 * W, C);
                 }
-                a.wpack = at(wpackd + (size_t)z * 9 * C * C * p.es); a.dst[0] = dx;
+                a.wpack = (const char*)wpackd + (size_t)z * 9 * C * C * es; a.dst[0] = dx;
                 a.res[0] = z > 0 ? dx : nullptr;
                 if (dx_planes) set_unshuffle(a, N, H, W);
                 if (z == 3) { a.aux[0] = aux; a.mask_mode = mask; a.sign_bits[0] = aux ? sign_bits : nullptr; }
@@ -350,18 +349,110 @@ struct Ctx {
             }
             return VSR_OK;
         }
-        ConvArgs a = base(N, H, W);
+        ConvArgs a = conv_args(N, H, W, C);
         a.nz = 1; a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
         for (int s = 0; s < 4; ++s) { a.src[s] = dy; a.src_oy[s] = s >> 1; a.src_ox[s] = s & 1; a.src_nstride[s] = pm_image_elems(2 * H, 2 * W, C); }
-        a.wpack = at(wpackd); a.dst[0] = dx; a.aux[0] = aux; a.mask_mode = mask;
-        return vsr_launch_conv(dtype, 3, 4, C, C, 0, p.CO, EPI_NHWC, a, st);
+        a.wpack = wpackd; a.dst[0] = dx; a.aux[0] = aux; a.mask_mode = mask;
+        return vsr_launch_conv(dtype, 3, 4, C, C, 0, CO, EPI_NHWC, a, st);
     }
-    int pack(const float* w, size_t dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
+    // weight gradients: one launch per pixel-shuffle phase z over the nseg (X, dY) pairs, X = the layer's input (N,H,W,C), dY = phase z
+    // of the gradient into it (a contiguous plane when dy_planes, else every second pixel of every second row of the 2H x 2W image)
+    int ps_wgrads(const void* const* x, const void* const* dy, int nseg, bool dy_planes, int N, int H, int W, float* gw, float* gb, int accumulate) const {
+        for (int z = 0; z < 4; ++z) {
+            WgradArgs a = wg_base(N, H, W, C, C);
+            a.nseg = nseg;
+            for (int i = 0; i < nseg; ++i) {
+                a.x[i] = x[i];
+                a.dy[i] = dy_planes ? (const char*)dy[i] + (size_t)z * plane_elems(N, 2 * H, 2 * W) * es : dy[i];      // plane z: N x H x W, contiguous
+            }
+            if (!dy_planes) { a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C); }
+            CK(wgrad(a, {3, C, false, C, false}, {C, C, gw, C, 0, 4, z, gb, accumulate}));
+        }
+        return VSR_OK;
+    }
+
+    // ---- the ResidualBlock stem (conv.py:97): conv3x3 on cat([lr(3), feat(C)]) (cat) or on lr alone ----
+    // cat: source 0 = feat = input channels 3..C+2, source 1 = LR = 0..2 (basicvsr.py:56,71): two weight sets, feat's first
+    int pack_stem(const float* w, void* dst, bool cat) const {
+        const int I_total = cat ? C + 3 : 3;
+        if (cat) CK(pack(w, dst, 9, CO, C, C, C, I_total, 3, 1, 0, 0));
+        return pack(w, (char*)dst + (cat ? (size_t)9 * CO * C * es : 0), 9, CO, 16, C, 3, I_total, 0, 1, 0, 0);
+    }
+    // data-gradient weights: towards feat (conv(3, ...) runs them), towards the 3 LR channels (conv_planar3)
+    int pack_stem_dgrad(const float* w, void* dst) const { return pack(w, dst, 9, CO, C, C, C, C + 3, 3, 1, 0, 1); }
+    int pack_stem_dlr(const float* w, void* dst, bool cat) const { return pack(w, dst, 9, 32, C, 3, C, cat ? C + 3 : 3, 0, 1, 0, 1); }
+    // feat: null => zeros (first frame of a direction); lr: planar fp32, lr_nstride floats between images
+    int stem(bool cat, const void* feat, const float* lr, long long lr_nstride, const void* wpack, const float* bias, void* y, int act, float slope,
+             int N, int H, int W) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.wpack = wpack; a.bias = bias; a.dst[0] = y; a.act = act; a.leaky_slope = slope;
+        a.src[cat ? 1 : 0] = lr; a.src_nstride[cat ? 1 : 0] = lr_nstride;
+        if (!cat) return vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st);
+        a.src[0] = feat;
+        return vsr_launch_conv(dtype, 3, 2, C, 16, 1, CO, EPI_NHWC, a, st);
+    }
+    // a_lr: X = the planar LR frames (+ the bias gradient); a_feat (cat, skipped without segments): X = feat
+    int stem_wgrads(bool cat, WgradArgs& a_lr, WgradArgs& a_feat, float* gw, float* gb, int accumulate) const {
+        const int I_total = cat ? C + 3 : 3;
+        CK(wgrad(a_lr, {3, 16, true, C, false}, {C, 3, gw, I_total, 0, 1, 0, gb, accumulate}));
+        if (cat && a_feat.nseg) CK(wgrad_cc(3, a_feat, gw, I_total, 3, nullptr, accumulate));
+        return VSR_OK;
+    }
+
+    // ---- SPyNet layer j (spynet.py:16-18) ----
+    // mode 0: forward weights; mode 1: data-gradient weights, rows = the conv's input channels (template COUT of the dgrad launch), K = its outputs
+    int pack_spy(int j, const float* w, void* dst, int mode) const {
+        if (mode == 0) return pack(w, dst, 49, SPY_COP[j], SPY_CIP[j], SPY_CO[j], SPY_CI[j], SPY_CI[j], 0, 1, 0, 0);
+        return pack(w, dst, 49, SPY_DROWS[j], SPY_DK[j], SPY_CI[j], SPY_CO[j], SPY_CI[j], 0, 1, 0, 1);
+    }
+    // y: pixel-major with SPY_CD[j] channels (j < 4) or planar fp32 (N,2,H,W) (+ pres) for the last layer
+    int spy_conv(int j, const void* x, const void* wpack, const float* bias, void* y, int act, float slope, const float* pres, int N, int H, int W) const {
+        ConvArgs a = conv_args(N, H, W, SPY_CD[j]);
+        a.src[0] = x; a.src_nstride[0] = pm_image_elems(H, W, SPY_CIP[j]);
+        a.wpack = wpack; a.bias = bias; a.act = act; a.leaky_slope = slope; a.cout_real = SPY_CO[j]; a.dst[0] = y;
+        if (j < NSPY - 1) return vsr_launch_conv(dtype, 7, 1, SPY_CIP[j], SPY_CIP[j], 0, SPY_COP[j], EPI_NHWC, a, st);
+        a.dst_nstride = (long long)2 * H * W; a.pres = pres;
+        return vsr_launch_conv(dtype, 7, 1, 16, 16, 0, 32, EPI_PLANAR, a, st);
+    }
+    // dX_j = dgrad(conv_j)(dY_j) (* ReLU'(aux)); dy: pixel-major with SPY_DK[j] channels
+    int spy_dgrad(int j, const void* dy, const void* wpackd, void* dx, const void* aux, int N, int H, int W) const {
+        const int CI = SPY_CIP[j], DK = SPY_DK[j];
+        ConvArgs a = conv_args(N, H, W, CI);
+        a.src[0] = dy; a.src_nstride[0] = pm_image_elems(H, W, DK);
+        a.wpack = wpackd; a.dst[0] = dx; a.cout_real = j == 0 ? 8 : CI;
+        if (aux) { a.aux[0] = aux; a.mask_mode = MASK_RELU; }
+        return vsr_launch_conv(dtype, 7, 1, DK, DK, 0, SPY_DROWS[j], EPI_NHWC, a, st);
+    }
+    int spy_wgrad(int j, const void* x, const void* dy, int N, int H, int W, float* gw, float* gb, int accumulate) const {
+        const int CI = SPY_CIP[j], DK = SPY_DK[j];
+        // fp32, 64 input channels: two 32-channel halves (the 14x38-pixel fp32 tile of 64 channels exceeds LDS)
+        const int nhalf = (dtype == VSR_F32 && CI == 64) ? 2 : 1;
+        for (int hf = 0; hf < nhalf; ++hf) {
+            WgradArgs a = wg_base(N, H, W, CI, DK);
+            a.x[0] = x; a.dy[0] = dy;
+            const int cx = CI / nhalf;
+            if (nhalf == 2) { a.x_ctotal = CI; a.x_coff = hf * (cx / 8); }
+            const int cin_real = nhalf == 2 ? cx : SPY_CI[j];
+            CK(wgrad(a, {7, cx, false, DK, false}, {SPY_CO[j], cin_real, gw, SPY_CI[j], hf * cx, 1, 0, hf == 0 ? gb : nullptr, accumulate}));
+        }
+        return VSR_OK;
+    }
+
+    // ---- weight gradients: one launch into this stream's slab buffer + its reduction (host.h) ----
+    int wgrad(WgradArgs& a, const WgradShape& s, const WgradDst& d, bool even = true) const { return wgrad_run(st, dtype, slab, a, s, d, even); }
+    // C -> C (3x3 / 1x1) into input channels [i_off, i_off + C) of gw's I_total
+    int wgrad_cc(int ks, WgradArgs& a, float* gw, int I_total, int i_off, float* gb, int accumulate) const {
+        return wgrad(a, {ks, C, false, C, false}, {C, C, gw, I_total, i_off, 1, 0, gb, accumulate});
+    }
+
+    // C -> C (3x3 / 1x1): mode 0 forward, 1 data gradient (flipped, transposed)
+    int pack_cc(int ks, const float* w, void* dst, int mode) const { return pack(w, dst, ks * ks, CO, C, C, C, C, 0, 1, 0, mode); }
+    int pack(const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
              int o_add, int mode) const {
-        return pack_any(dtype, w, at(dst), KK, RP, CPd, r_real, c_real, I_total, i_off, o_mul, o_add, mode);
+        return pack_any(dtype, w, dst, KK, RP, CPd, r_real, c_real, I_total, i_off, o_mul, o_add, mode);
     }
-    int pack_bias(const float* b, size_t dst, int nreal, int o_mul = 1, int o_add = 0) const {
-        return pack_any(VSR_F32, b, at(dst), 1, nreal, 1, nreal, 1, 1, 0, o_mul, o_add, 0);
+    int pack_bias(const float* b, void* dst, int nreal, int o_mul = 1, int o_add = 0) const {
+        return pack_any(VSR_F32, b, dst, 1, nreal, 1, nreal, 1, 1, 0, o_mul, o_add, 0);
     }
     int pack_any(int dt, const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
                  int o_add, int mode) const {
@@ -375,6 +466,11 @@ struct Ctx {
         return VSR_OK;
     }
 };
+
+// lane 0: the caller's stream, 1: the helper stream (selects the per-stream weight-gradient slab buffer)
+Ctx engine_ctx(const Plan& p, char* ws, hipStream_t st, int lane) {
+    return Ctx(ws, st, p.dtype, p.C, p.bwd ? reinterpret_cast<float*>(ws + p.slab[lane]) : nullptr);
+}
 
 // parameter index helpers (order documented in vsrlab_hip.h)
 struct PIdx {
@@ -409,10 +505,9 @@ int spynet_pack(const Ctx& c, const SpyPlan& sp, const float* const* params, int
         for (int j = 0; j < NSPY; ++j) {
             const float* w = params[base_idx + (l * NSPY + j) * 2];
             const float* b = params[base_idx + (l * NSPY + j) * 2 + 1];
-            CK(c.pack(w, sp.wpack[l][j], 49, SPY_COP[j], SPY_CIP[j], SPY_CO[j], SPY_CI[j], SPY_CI[j], 0, 1, 0, 0));
-            CK(c.pack_bias(b, sp.bias[l][j], SPY_CO[j]));
-            // data-gradient weights: rows = the conv's input channels (template COUT of the dgrad launch), K = its outputs
-            if (sp.save) CK(c.pack(w, sp.wpackd[l][j], 49, SPY_DROWS[j], SPY_DK[j], SPY_CI[j], SPY_CO[j], SPY_CI[j], 0, 1, 0, 1));
+            CK(c.pack_spy(j, w, c.at(sp.wpack[l][j]), 0));
+            CK(c.pack_bias(b, c.at(sp.bias[l][j]), SPY_CO[j]));
+            if (sp.save) CK(c.pack_spy(j, w, c.at(sp.wpackd[l][j]), 1));
         }
     return VSR_OK;
 }
@@ -435,22 +530,13 @@ int spynet_run(const Ctx& c, const SpyPlan& sp, const float* frames, const float
         CK(vsr_launch_spynet_prepare(c.dtype, c.fat(sp.pyr[l]), l == 0 ? nullptr : c.fat(fprev), (float*)c.at(fup), c.at(bufs[0]),
                                      n, t, P, pair_mode, hl, wl, l == 0, c.st));
         for (int j = 0; j < NSPY; ++j) {
-            ConvArgs a = c.base(P, hl, wl);
-            a.src[0] = c.at(bufs[j]); a.src_nstride[0] = pm_image_elems(hl, wl, SPY_CIP[j]);
-            a.wpack = c.at(sp.wpack[l][j]); a.bias = c.fat(sp.bias[l][j]);
-            a.act = (j < NSPY - 1 || last_relu) ? ACT_RELU : ACT_NONE;     // RealBasicVSR's Spynet: ReLU after the LAST conv too (spynet.py:16-18)
-            a.cout_real = SPY_CO[j];
-            if (j < NSPY - 1) {
-                a.dst[0] = c.at(bufs[j + 1]); a.CD = SPY_CD[j]; a.dst_nstride = pm_image_elems(hl, wl, SPY_CD[j]);
-                CK(vsr_launch_conv(c.dtype, 7, 1, SPY_CIP[j], SPY_CIP[j], 0, SPY_COP[j], EPI_NHWC, a, c.st));
-            } else if (!sp.save) {
-                a.dst[0] = c.at(fcur); a.dst_nstride = (long long)2 * hl * wl; a.pres = c.fat(fup);   // flow = flow_up + residue (spynet.py:65)
-                CK(vsr_launch_conv(c.dtype, 7, 1, 16, 16, 0, 32, EPI_PLANAR, a, c.st));
-            } else {                                           // keep the residue: its sign is the last ReLU's mask
-                a.dst[0] = c.at(sp.sres[l]); a.dst_nstride = (long long)2 * hl * wl;
-                CK(vsr_launch_conv(c.dtype, 7, 1, 16, 16, 0, 32, EPI_PLANAR, a, c.st));
+            const int act = (j < NSPY - 1 || last_relu) ? ACT_RELU : ACT_NONE;     // RealBasicVSR's Spynet: ReLU after the LAST conv too (spynet.py:16-18)
+            // the last layer: flow = flow_up + residue (spynet.py:65); save: keep the residue, its sign is the last ReLU's mask
+            void* y = j < NSPY - 1 ? c.at(bufs[j + 1]) : c.at(sp.save ? sp.sres[l] : fcur);
+            const float* pres = (j == NSPY - 1 && !sp.save) ? c.fat(fup) : nullptr;
+            CK(c.spy_conv(j, c.at(bufs[j]), c.at(sp.wpack[l][j]), c.fat(sp.bias[l][j]), y, act, 0.f, pres, P, hl, wl));
+            if (j == NSPY - 1 && sp.save)
                 CK(vsr_launch_add_f32(c.fat(fup), c.fat(sp.sres[l]), (float*)c.at(fcur), (long long)P * 2 * hl * wl, c.st));
-            }
         }
         if (level_out && level_out[l])
             CK(vsr_launch_flow_out(c.fat(fcur), level_out[l], P, hl, wl, sp.h >> (5 - l), sp.w >> (5 - l), c.st));
@@ -474,41 +560,36 @@ int pack_all(const Ctx& c, const Plan& p, const float* const* prm) {
 
 int pack_all_collect(const Ctx& c, const Plan& p, const float* const* prm) {
     const PIdx ix{p.rb, p.ups};
-    const int dt = c.dtype; (void)dt;
     const int C = p.C, CO = p.CO;           // (CO: packed rows of a C-output weight set)
     for (int dir = 0; dir < 2; ++dir) {
         const float* sw = prm[ix.stem_w(dir)];
-        // cat([lr_i(3), feat(C)]) (basicvsr.py:56,71): source 0 = feat = input channels 3..C+2, source 1 = LR = 0..2
-        CK(c.pack(sw, p.stem_w[dir], 9, CO, C, C, C, C + 3, 3, 1, 0, 0));
-        CK(c.pack(sw, p.stem_w[dir] + (size_t)9 * CO * C * p.es, 9, CO, 16, C, 3, C + 3, 0, 1, 0, 0));
-        CK(c.pack_bias(prm[ix.stem_b(dir)], p.stem_b[dir], C));
-        if (p.bwd) CK(c.pack(sw, p.stem_wd[dir], 9, CO, C, C, C, C + 3, 3, 1, 0, 1));
-        if (p.flowgrad) CK(c.pack(sw, p.stem_wd_lr[dir], 9, 32, C, 3, C, C + 3, 0, 1, 0, 1));
+        CK(c.pack_stem(sw, c.at(p.stem_w[dir]), true));
+        CK(c.pack_bias(prm[ix.stem_b(dir)], c.at(p.stem_b[dir]), C));
+        if (p.bwd) CK(c.pack_stem_dgrad(sw, c.at(p.stem_wd[dir])));
+        if (p.flowgrad) CK(c.pack_stem_dlr(sw, c.at(p.stem_wd_lr[dir]), true));
         for (int k = 0; k < 2 * p.rb; ++k) {
-            CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_w[dir][k], 9, CO, C, C, C, C, 0, 1, 0, 0));
-            if (p.bwd) CK(c.pack(prm[ix.blk_w(dir, k)], p.blk_wd[dir][k], 9, CO, C, C, C, C, 0, 1, 0, 1));
-            CK(c.pack_bias(prm[ix.blk_b(dir, k)], p.blk_b[dir][k], C));
+            CK(c.pack_cc(3, prm[ix.blk_w(dir, k)], c.at(p.blk_w[dir][k]), 0));
+            if (p.bwd) CK(c.pack_cc(3, prm[ix.blk_w(dir, k)], c.at(p.blk_wd[dir][k]), 1));
+            CK(c.pack_bias(prm[ix.blk_b(dir, k)], c.at(p.blk_b[dir][k]), C));
         }
     }
     for (int s = 0; s < 2; ++s) {
-        CK(c.pack(prm[ix.point_w()], p.point_w + (size_t)s * CO * C * p.es, 1, CO, C, C, C, 2 * C, s * C, 1, 0, 0));
-        if (p.bwd) CK(c.pack(prm[ix.point_w()], p.point_wd + (size_t)s * CO * C * p.es, 1, CO, C, C, C, 2 * C, s * C, 1, 0, 1));
+        CK(c.pack(prm[ix.point_w()], c.at(p.point_w + (size_t)s * CO * C * p.es), 1, CO, C, C, C, 2 * C, s * C, 1, 0, 0));
+        if (p.bwd) CK(c.pack(prm[ix.point_w()], c.at(p.point_wd + (size_t)s * CO * C * p.es), 1, CO, C, C, C, 2 * C, s * C, 1, 0, 1));
     }
-    CK(c.pack_bias(prm[ix.point_b()], p.point_b, C));
-    for (int k = 0; k < p.ups; ++k)
-        for (int z = 0; z < 4; ++z) {
-            // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c+2i+j, y, x]  => sub-conv z uses rows 4c+z
-            CK(c.pack(prm[ix.up_w(k)], p.up_w[k] + (size_t)z * 9 * CO * C * p.es, 9, CO, C, C, C, C, 0, 4, z, 0));
-            if (p.bwd) CK(c.pack(prm[ix.up_w(k)], p.up_wd[k] + (size_t)z * 9 * CO * C * p.es, 9, CO, C, C, C, C, 0, 4, z, 1));
-            CK(c.pack_bias(prm[ix.up_b(k)], p.up_b[k] + (size_t)z * C * 4, C, 4, z));
-        }
+    CK(c.pack_bias(prm[ix.point_b()], c.at(p.point_b), C));
+    for (int k = 0; k < p.ups; ++k) {
+        CK(c.pack_ps(prm[ix.up_w(k)], c.at(p.up_w[k]), 0));
+        if (p.bwd) CK(c.pack_ps(prm[ix.up_w(k)], c.at(p.up_wd[k]), 1));
+        CK(c.pack_ps_bias(prm[ix.up_b(k)], (float*)c.at(p.up_b[k])));
+    }
     // conv_last.0: C -> 64 (basicvsr.py:20); its data gradient 64 -> C
-    CK(c.pack(prm[ix.last0_w()], p.last0_w, 9, 64, C, 64, C, C, 0, 1, 0, 0));
-    if (p.bwd) CK(c.pack(prm[ix.last0_w()], p.last0_wd, 9, CO, 64, C, 64, C, 0, 1, 0, 1));
-    CK(c.pack_bias(prm[ix.last0_b()], p.last0_b, 64));
-    CK(c.pack(prm[ix.last2_w()], p.last2_w, 9, 32, 64, 3, 64, 64, 0, 1, 0, 0));
-    if (p.bwd) CK(c.pack(prm[ix.last2_w()], p.last2_wd, 9, 64, 16, 64, 3, 64, 0, 1, 0, 1));
-    CK(c.pack_bias(prm[ix.last2_b()], p.last2_b, 3));
+    CK(c.pack(prm[ix.last0_w()], c.at(p.last0_w), 9, 64, C, 64, C, C, 0, 1, 0, 0));
+    if (p.bwd) CK(c.pack(prm[ix.last0_w()], c.at(p.last0_wd), 9, CO, 64, C, 64, C, 0, 1, 0, 1));
+    CK(c.pack_bias(prm[ix.last0_b()], c.at(p.last0_b), 64));
+    CK(c.pack(prm[ix.last2_w()], c.at(p.last2_w), 9, 32, 64, 3, 64, 64, 0, 1, 0, 0));
+    if (p.bwd) CK(c.pack(prm[ix.last2_w()], c.at(p.last2_wd), 9, 64, 16, 64, 3, 64, 0, 1, 0, 1));
+    CK(c.pack_bias(prm[ix.last2_b()], c.at(p.last2_b), 3));
     if (p.t > 1) CK(spynet_pack(c, p.spy, prm, ix.spy_base()));
     return VSR_OK;
 }
@@ -574,12 +655,8 @@ int trunk_chain_backward(const Ctx& c, const Plan& p, int dir, int i) {
 int trunk_forward(const Ctx& c, const Plan& p, int dir, int i, const void* warped, const float* lrs) {
     const int n = p.n, h = p.h, w = p.w, rb = p.rb;
     void* x = p.bwd ? c.at(p.xoff(dir, i, 0)) : c.at(p.feat[dir][i]);
-    {
-        ConvArgs a = c.base(n, h, w);
-        a.src[0] = warped;                                   // null => zeros (first frame of the direction)
-        a.src[1] = lrs + (size_t)i * 3 * h * w; a.src_nstride[1] = (long long)p.t * 3 * h * w;
-        a.wpack = c.at(p.stem_w[dir]); a.bias = c.fat(p.stem_b[dir]); a.dst[0] = x; a.act = ACT_LEAKY;
-        CK(vsr_launch_conv(c.dtype, 3, 2, p.C, 16, 1, p.CO, EPI_NHWC, a, c.st));
+    {   // warped: null => zeros (first frame of the direction)
+        CK(c.stem(true, warped, lrs + (size_t)i * 3 * h * w, (long long)p.t * 3 * h * w, c.at(p.stem_w[dir]), c.fat(p.stem_b[dir]), x, ACT_LEAKY, 0.f, n, h, w));
         // the stem runs on the generic two-source kernel: its LeakyReLU sign bits for the block-0 data gradient come from a 66 MB pass
         if (p.sb) CK(vsr_launch_sign_bits_c64(x, c.at(p.SBX0[dir][i]), n, h, w, c.st));
     }
@@ -587,9 +664,9 @@ int trunk_forward(const Ctx& c, const Plan& p, int dir, int i, const void* warpe
     for (int b = 0; b < rb; ++b) {      // x + conv2(relu(conv1(x)))   (conv.py:89-92)
         void* act = p.bwd ? c.at(p.aoff(dir, i, b)) : c.at(p.scratchA[dir]);
         void* xn = p.bwd ? c.at(p.xoff(dir, i, b + 1)) : x;   // inference: in place (residual read = own pixel)
-        CK(c.conv64(x, p.blk_w[dir][2 * b], c.fat(p.blk_b[dir][2 * b]), act, ACT_RELU, nullptr, nullptr, 0, n, h, w,
+        CK(c.conv(3, x, c.at(p.blk_w[dir][2 * b]), c.fat(p.blk_b[dir][2 * b]), act, ACT_RELU, nullptr, nullptr, 0, n, h, w,
                     p.sb ? c.at(p.sboff(dir, i, b)) : nullptr));
-        CK(c.conv64(act, p.blk_w[dir][2 * b + 1], c.fat(p.blk_b[dir][2 * b + 1]), xn, ACT_NONE, x, nullptr, 0, n, h, w));
+        CK(c.conv(3, act, c.at(p.blk_w[dir][2 * b + 1]), c.fat(p.blk_b[dir][2 * b + 1]), xn, ACT_NONE, x, nullptr, 0, n, h, w));
         x = xn;
     }
     return VSR_OK;
@@ -599,8 +676,8 @@ int trunk_forward(const Ctx& c, const Plan& p, int dir, int i, const void* warpe
 int last0_forward(const Ctx& c, const Plan& p, int i, void* sign_out) {
     const int S = p.scale;
     if (p.C == 64)
-        return c.conv64(c.at(p.U1[i]), p.last0_w, c.fat(p.last0_b), c.at(p.C0[i]), ACT_LEAKY, nullptr, nullptr, 0, p.n, S * p.h, S * p.w, sign_out);
-    ConvArgs a = c.base(p.n, S * p.h, S * p.w);
+        return c.conv(3, c.at(p.U1[i]), c.at(p.last0_w), c.fat(p.last0_b), c.at(p.C0[i]), ACT_LEAKY, nullptr, nullptr, 0, p.n, S * p.h, S * p.w, sign_out);
+    ConvArgs a = conv_args(p.n, S * p.h, S * p.w, c.C);
     a.src[0] = c.at(p.U1[i]); a.wpack = c.at(p.last0_w); a.bias = c.fat(p.last0_b); a.dst[0] = c.at(p.C0[i]); a.act = ACT_LEAKY;
     a.CD = 64; a.cout_real = 64; a.dst_nstride = pm_image_elems(S * p.h, S * p.w, 64);
     return vsr_launch_conv(c.dtype, 3, 1, p.C, p.C, 0, 64, EPI_NHWC, a, c.st);
@@ -609,18 +686,18 @@ int last0_forward(const Ctx& c, const Plan& p, int i, void* sign_out) {
 int recon_forward(const Ctx& c, const Plan& p, int i, const float* lrs, float* sr) {
     const int n = p.n, h = p.h, w = p.w;
     {
-        ConvArgs a = c.base(n, h, w);       // point_conv on cat([outputs[i], feat_prop]) (basicvsr.py:75-77)
+        ConvArgs a = conv_args(n, h, w, c.C);       // point_conv on cat([outputs[i], feat_prop]) (basicvsr.py:75-77)
         a.src[0] = c.at(p.feat[0][i]); a.src[1] = c.at(p.feat[1][i]);
         a.wpack = c.at(p.point_w); a.bias = c.fat(p.point_b); a.dst[0] = c.at(p.Pt[i]); a.act = ACT_LEAKY;
         CK(vsr_launch_conv(c.dtype, 1, 2, p.C, p.C, 0, p.CO, EPI_NHWC, a, c.st));
         if (p.sb) CK(vsr_launch_sign_bits_c64(c.at(p.Pt[i]), c.at(p.SBPt[i]), n, h, w, c.st));   // mask of upsample.0's data gradient
     }
     const int S = p.scale;                     // upscale: S / 2 PixelShufflePacks (basicvsr.py:19); U1 = U0 for S = 2 (Plan::build)
-    CK(c.conv_ps(c.at(p.Pt[i]), p.up_w[0], c.fat(p.up_b[0]), c.at(p.U0[i]), n, h, w));
-    if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), p.up_w[1], c.fat(p.up_b[1]), c.at(p.U1[i]), n, 2 * h, 2 * w));
+    CK(c.conv_ps(c.at(p.Pt[i]), c.at(p.up_w[0]), c.fat(p.up_b[0]), c.at(p.U0[i]), n, h, w));
+    if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), c.at(p.up_w[1]), c.fat(p.up_b[1]), c.at(p.U1[i]), n, 2 * h, 2 * w));
     CK(last0_forward(c, p, i, p.sb ? c.at(p.SBC0[i]) : nullptr));
     {
-        ConvArgs a = c.base(n, S * h, S * w);   // conv_last.2 + bilinear xS skip (basicvsr.py:21-22,82)
+        ConvArgs a = conv_args(n, S * h, S * w, c.C);   // conv_last.2 + bilinear xS skip (basicvsr.py:21-22,82)
         a.src_nstride[0] = pm_image_elems(S * h, S * w, 64);
         a.src[0] = c.at(p.C0[i]); a.wpack = c.at(p.last2_w); a.bias = c.fat(p.last2_b); a.cout_real = 3;
         a.dst[0] = sr + (size_t)i * 3 * S * S * h * w; a.dst_nstride = (long long)p.t * 3 * S * S * h * w;
@@ -694,7 +771,7 @@ int forward_chain(const Ctx& c, const Plan& p, int dir, const float* lrs) {
 }
 
 int forward_impl(const Plan& p, const float* const* prm, const float* lrs, float* sr, char* ws, hipStream_t st) {
-    const Ctx c{p, ws, st, p.dtype, 0};
+    const Ctx c = engine_ctx(p, ws, st, 0);
     const PIdx ix{p.rb, p.ups};
     const int n = p.n, t = p.t;
     CK(pack_all(c, p, prm));
@@ -704,7 +781,7 @@ int forward_impl(const Plan& p, const float* const* prm, const float* lrs, float
         // (chain launches spin on each other's tiles: two of them side by side could each hold the CUs the other's unstarted
         // workgroups need -- conv3x3_chain.hip, "Work distribution" -- so with the chains on, both directions share the caller's stream)
         CK(f.begin(!chain_on(p)));
-        const Ctx c0{p, ws, st, p.dtype, 0}, c1{p, ws, f.side(), p.dtype, 1};
+        const Ctx c0 = engine_ctx(p, ws, st, 0), c1 = engine_ctx(p, ws, f.side(), 1);
         CK(forward_chain(c0, p, 0, lrs));
         CK(forward_chain(c1, p, 1, lrs));
         CK(f.end());
@@ -714,41 +791,6 @@ int forward_impl(const Plan& p, const float* const* prm, const float* lrs, float
 }
 
 // ---- backward ------------------------------------------------------------------------------------
-struct WG {   // one weight-gradient launch + reduction
-    const Ctx& c;
-    int run(int ks, int cx, bool xp, int cout, bool dyp, WgradArgs& a, int cout_real, int cin_real, float* gw, int I_total,
-            int i_off, int o_mul, int o_add, float* gb) const {
-        if (!gw && !gb) return VSR_OK;
-        int cp, xpd, stride;
-        vsr_wgrad_slab_dims(ks, cx, cout, &cp, &xpd, &stride);
-        a.slab = (float*)c.at(c.p.slab[c.lane]); a.slab_stride = stride;
-        const int tiles = a.N * cdiv(a.H, 8) * cdiv(a.W, 32);
-        int cp3, xp3, stride3;
-        vsr_wgrad_slab_dims(3, 64, 64, &cp3, &xp3, &stride3);          // the slab buffer holds VSR_WGRAD_NWG of these
-        const long long cap = (long long)VSR_WGRAD_NWG * stride3 / stride;
-        int nwg = tiles < VSR_WGRAD_NWG ? tiles : VSR_WGRAD_NWG;
-        if (nwg > cap) nwg = (int)cap;
-        if (nwg > 1) nwg &= ~1;
-        int nslabs = 0;
-        if (c.dtype == VSR_BF16 && ks == 3 && cx == 64 && !xp && cout == 16 && dyp && a.nseg == 1 && a.x_step == 1 && a.dy_step == 1 &&
-            a.Hx == a.H && a.Wx == a.W && a.Hy == a.H && a.Wy == a.W) {
-            // 64 -> 3 conv with a planar cotangent (conv_last.2, the pre-clean out conv): streaming kernel of hr_tail.hip
-            CK(vsr_launch_last2_wgrad(a.x[0], reinterpret_cast<const float*>(a.dy[0]), a.dy_nstride, a.slab, stride, a.N, a.H, a.W, &nslabs, c.st));
-        } else
-        CK(vsr_launch_wgrad(c.dtype, ks, cx, xp, cout, dyp, a, nwg, &nslabs, c.st));
-        if (!gw) return VSR_ERR_BADARG;
-        return vsr_launch_wgrad_reduce(a.slab, nslabs, ks, cx, cout, cout_real, cin_real, gw, I_total, i_off, o_mul, o_add, gb, 1, c.st);
-    }
-};
-
-WgradArgs wg_base(int N, int H, int W, int Cx = C, int Cy = C) {       // Cx / Cy: channels of the pixel-major X / dY
-    WgradArgs a = {};
-    a.N = N; a.H = H; a.W = W; a.nseg = 1;
-    a.x_step = 1; a.Hx = H; a.Wx = W; a.x_nstride = pm_image_elems(H, W, Cx);
-    a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, Cy);
-    return a;
-}
-
 // Backward of spynet_run for train_flow (spynet.py:38-93): dflows_out = d loss / d flows (P,2,h,w) ->
 // weight / bias gradients of the 6 x 5 convs (g[base_idx ...], OIHW fp32).  The frames are not differentiated.
 // dframes (optional): (F,3,h,w) fp32, ACCUMULATED into: the gradient w.r.t. the input frames (through the pyramid).
@@ -757,7 +799,6 @@ WgradArgs wg_base(int N, int H, int W, int Cx = C, int Cy = C) {       // Cx / C
 int spynet_backward(const Ctx& c, const SpyPlan& sp, const float* dflows_out, int n, int t, int pair_mode, float* const* g,
                     int base_idx, float* dframes = nullptr, const float* std = nullptr, bool last_relu = true,
                     const float* const* dlevel = nullptr) {
-    const WG wg{c};
     const int P = sp.P, hu = sp.hu, wu = sp.wu;
     size_t dcur = sp.dfa, dprev = sp.dfb;
     HIP_CHECK_RET(hipMemsetAsync(c.at(dcur), 0, (size_t)P * 2 * hu * wu * 4, c.st));
@@ -773,31 +814,13 @@ int spynet_backward(const Ctx& c, const SpyPlan& sp, const float* dflows_out, in
         CK(vsr_launch_spynet_dres(c.dtype, c.fat(dcur), last_relu ? c.fat(sp.sres[l]) : nullptr, c.at(sp.dres), P, hl, wl, c.st));
         size_t dy = sp.dres;
         for (int j = NSPY - 1; j >= 0; --j) {
-            const int CI = SPY_CIP[j], CO = SPY_DK[j];
             float* gw = g ? g[base_idx + (l * NSPY + j) * 2] : nullptr;
             float* gb = g ? g[base_idx + (l * NSPY + j) * 2 + 1] : nullptr;
-            if (gw || gb) {
-                // fp32, 64 input channels: two 32-channel halves (the 14x38-pixel fp32 tile of 64 channels exceeds LDS)
-                const int nhalf = (c.dtype == VSR_F32 && CI == 64) ? 2 : 1;
-                for (int hf = 0; hf < nhalf; ++hf) {
-                    WgradArgs a = wg_base(P, hl, wl);
-                    a.x[0] = c.at(sp.sx[l][j]); a.x_nstride = pm_image_elems(hl, wl, CI);
-                    a.dy[0] = c.at(dy); a.dy_nstride = pm_image_elems(hl, wl, CO);
-                    const int cx = CI / nhalf;
-                    if (nhalf == 2) { a.x_ctotal = CI; a.x_coff = hf * (cx / 8); }
-                    const int cin_real = nhalf == 2 ? cx : SPY_CI[j];
-                    CK(wg.run(7, cx, false, CO, false, a, SPY_CO[j], cin_real, gw, SPY_CI[j], hf * cx, 1, 0, hf == 0 ? gb : nullptr));
-                }
-            }
+            CK(c.spy_wgrad(j, c.at(sp.sx[l][j]), c.at(dy), P, hl, wl, gw, gb, 1));
             if (j == 0 && l == 0 && !dframes) break;       // level 0's input depends on the frames only
             // dX_j = dgrad(conv_j)(dY_j) (* ReLU'(X_j) for j > 0: X_j is the previous conv's ReLU output)
             const size_t dx = (dy == sp.gA) ? sp.gB : sp.gA;
-            ConvArgs a = c.base(P, hl, wl);
-            a.src[0] = c.at(dy); a.src_nstride[0] = pm_image_elems(hl, wl, CO);
-            a.wpack = c.at(sp.wpackd[l][j]); a.dst[0] = c.at(dx);
-            a.CD = CI; a.cout_real = j == 0 ? 8 : CI; a.dst_nstride = pm_image_elems(hl, wl, CI);
-            if (j > 0) { a.aux[0] = c.at(sp.sx[l][j]); a.mask_mode = MASK_RELU; }
-            CK(vsr_launch_conv(c.dtype, 7, 1, CO, CO, 0, SPY_DROWS[j], EPI_NHWC, a, c.st));
+            CK(c.spy_dgrad(j, c.at(dy), c.at(sp.wpackd[l][j]), c.at(dx), j > 0 ? c.at(sp.sx[l][j]) : nullptr, P, hl, wl));
             dy = dx;
         }
         float* dfr = dframes ? (float*)c.at(sp.dpyr[l]) : nullptr;
@@ -823,30 +846,19 @@ int spynet_backward(const Ctx& c, const SpyPlan& sp, const float* dflows_out, in
 // X = the layer's input, dY = phase z of the gradient into it (a contiguous plane when p.unsh, else every second pixel of every second row)
 int recon_ps_wgrads(const Ctx& c, const Plan& p, int k, int f0, int f1, float* const* g) {
     const PIdx ix{p.rb, p.ups};
-    const WG wg{c};
-    const int n = p.n, H = (k + 1) * p.h, W = (k + 1) * p.w;              // the layer's input size: h x w (k = 0), 2h x 2w (k = 1)
-    const int C = p.C;
+    const int H = (k + 1) * p.h, W = (k + 1) * p.w;              // the layer's input size: h x w (k = 0), 2h x 2w (k = 1)
     for (int i0 = f0; i0 < f1; i0 += VSR_WG_MAXSEG) {
         const int i1 = i0 + VSR_WG_MAXSEG < f1 ? i0 + VSR_WG_MAXSEG : f1;
-        for (int z = 0; z < 4; ++z) {
-            WgradArgs a = wg_base(n, H, W, C, C);
-            a.nseg = 0;
-            for (int i = i0; i < i1; ++i) {
-                a.x[a.nseg] = c.at(k == 1 ? p.U0[i] : p.Pt[i]);
-                const char* gu = (const char*)c.at(k == 1 ? p.GU1f[i] : p.GU0f[i]);
-                a.dy[a.nseg] = p.unsh ? gu + (size_t)z * Ctx::plane_elems(n, 2 * H, 2 * W) * p.es : gu;      // plane z: n x H x W, contiguous
-                ++a.nseg;
-            }
-            if (!p.unsh) { a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C); }
-            CK(wg.run(3, C, false, C, false, a, C, C, g[ix.up_w(k)], C, 0, 4, z, g[ix.up_b(k)]));
-        }
+        const void* x[VSR_WG_MAXSEG];
+        const void* dy[VSR_WG_MAXSEG];
+        for (int i = i0; i < i1; ++i) { x[i - i0] = c.at(k == 1 ? p.U0[i] : p.Pt[i]); dy[i - i0] = c.at(k == 1 ? p.GU1f[i] : p.GU0f[i]); }
+        CK(c.ps_wgrads(x, dy, i1 - i0, p.unsh, p.n, H, W, g[ix.up_w(k)], g[ix.up_b(k)], 1));
     }
     return VSR_OK;
 }
 // ... and of the 1x1 fuse conv on cat([outputs[i], feat_prop]) (basicvsr.py:18,75-77): one launch per 64-channel half of its input
 int recon_point_wgrads(const Ctx& c, const Plan& p, int f0, int f1, float* const* g) {
     const PIdx ix{p.rb, p.ups};
-    const WG wg{c};
     const int C = p.C;
     for (int i0 = f0; i0 < f1; i0 += VSR_WG_MAXSEG) {
         const int i1 = i0 + VSR_WG_MAXSEG < f1 ? i0 + VSR_WG_MAXSEG : f1;
@@ -854,7 +866,7 @@ int recon_point_wgrads(const Ctx& c, const Plan& p, int f0, int f1, float* const
             WgradArgs a = wg_base(p.n, p.h, p.w, C, C);
             a.nseg = 0;
             for (int i = i0; i < i1; ++i) { a.x[a.nseg] = c.at(p.feat[s][i]); a.dy[a.nseg] = c.at(p.GPf[i]); ++a.nseg; }
-            CK(wg.run(1, C, false, C, false, a, C, C, g[ix.point_w()], 2 * C, s * C, 1, 0, s == 0 ? g[ix.point_b()] : nullptr));
+            CK(c.wgrad_cc(1, a, g[ix.point_w()], 2 * C, s * C, s == 0 ? g[ix.point_b()] : nullptr, 1));
         }
     }
     return VSR_OK;
@@ -862,10 +874,9 @@ int recon_point_wgrads(const Ctx& c, const Plan& p, int f0, int f1, float* const
 
 int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const float* dsr, float* const* g, const float* last2_w) {
     const PIdx ix{p.rb, p.ups};
-    const WG wg{c};
     if (p.diet) {   // U0, U1 and C0 of this frame were not kept: the forward's three launches again (the sign bits of C0 were)
-        CK(c.conv_ps(c.at(p.Pt[i]), p.up_w[0], c.fat(p.up_b[0]), c.at(p.U0[i]), p.n, p.h, p.w));
-        if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), p.up_w[1], c.fat(p.up_b[1]), c.at(p.U1[i]), p.n, 2 * p.h, 2 * p.w));
+        CK(c.conv_ps(c.at(p.Pt[i]), c.at(p.up_w[0]), c.fat(p.up_b[0]), c.at(p.U0[i]), p.n, p.h, p.w));
+        if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), c.at(p.up_w[1]), c.fat(p.up_b[1]), c.at(p.U1[i]), p.n, 2 * p.h, 2 * p.w));
         CK(last0_forward(c, p, i, nullptr));
     }
     const int C = p.C;
@@ -875,7 +886,7 @@ int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const f
     if (c.dtype == VSR_BF16 && last2_w) {   // d(conv_last.0 pre-activation) = dgrad(conv_last.2)(dsr) * LeakyReLU'(C0): hr_tail.hip
         CK(vsr_launch_last2_dgrad(dsr_i, dsr_ns, last2_w, c.at(p.C0[i]), c.at(p.G_C0), n, H4, W4, MASK_LEAKY, c.st, p.sb ? c.at(p.SBC0[i]) : nullptr));
     } else {
-        ConvArgs a = c.base(n, H4, W4);
+        ConvArgs a = conv_args(n, H4, W4, c.C);
         a.src[0] = dsr_i; a.src_nstride[0] = dsr_ns; a.wpack = c.at(p.last2_wd); a.dst[0] = c.at(p.G_C0);
         a.aux[0] = c.at(p.C0[i]); a.mask_mode = MASK_LEAKY;
         a.CD = 64; a.cout_real = 64; a.dst_nstride = pm_image_elems(H4, W4, 64);
@@ -884,32 +895,32 @@ int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const f
     {   // conv_last.2: X = C0, dY = dsr (planar)
         WgradArgs a = wg_base(n, H4, W4, 64, 64);
         a.x[0] = c.at(p.C0[i]); a.dy[0] = dsr_i; a.dy_nstride = dsr_ns;
-        CK(wg.run(3, 64, false, 16, true, a, 3, 64, g[ix.last2_w()], 64, 0, 1, 0, g[ix.last2_b()]));
+        CK(c.wgrad(a, {3, 64, false, 16, true}, {3, 64, g[ix.last2_w()], 64, 0, 1, 0, g[ix.last2_b()], 1}));
     }
     // (r04: G_U1 / G_U0, the gradients into the pixel-shuffle layers, are written phase-separated when p.unsh)
     const size_t gu1 = p.GU1f[i], gu0 = p.GU0f[i], gp = p.GPf[i];     // (per frame when p.hrdef: their weight gradients run later, all frames per launch)
     if (C == 64) {
-        CK(c.conv64(c.at(p.G_C0), p.last0_wd, nullptr, c.at(gu1), ACT_NONE, nullptr, nullptr, 0, n, H4, W4, nullptr, nullptr, p.unsh));
+        CK(c.conv(3, c.at(p.G_C0), c.at(p.last0_wd), nullptr, c.at(gu1), ACT_NONE, nullptr, nullptr, 0, n, H4, W4, nullptr, nullptr, p.unsh));
     } else {    // conv_last.0's data gradient 64 -> C
-        ConvArgs a = c.base(n, H4, W4);
+        ConvArgs a = conv_args(n, H4, W4, c.C);
         a.src[0] = c.at(p.G_C0); a.src_nstride[0] = pm_image_elems(H4, W4, 64); a.wpack = c.at(p.last0_wd); a.dst[0] = c.at(gu1);
         CK(vsr_launch_conv(c.dtype, 3, 1, 64, 64, 0, p.CO, EPI_NHWC, a, c.st));
     }
     {   // conv_last.0: X = U1, dY = G_C0
         WgradArgs a = wg_base(n, H4, W4, C, 64);
         a.x[0] = c.at(p.U1[i]); a.dy[0] = c.at(p.G_C0);
-        CK(wg.run(3, C, false, 64, false, a, 64, C, g[ix.last0_w()], C, 0, 1, 0, g[ix.last0_b()]));
+        CK(c.wgrad(a, {3, C, false, 64, false}, {64, C, g[ix.last0_w()], C, 0, 1, 0, g[ix.last0_b()], 1}));
     }
     // upsample.1 (at 2h x 2w; upscale 4 only -- for upscale 2 G_U1 IS G_U0): dgrad, then wgrad per pixel-shuffle phase z
     if (p.ups == 2) {
-        CK(c.conv_ps_dgrad(c.at(gu1), p.up_wd[1], c.at(gu0), nullptr, 0, n, 2 * h, 2 * w, nullptr, p.unsh, p.unsh));
+        CK(c.conv_ps_dgrad(c.at(gu1), c.at(p.up_wd[1]), c.at(gu0), nullptr, 0, n, 2 * h, 2 * w, nullptr, p.unsh, p.unsh));
         if (!p.hrdef) CK(recon_ps_wgrads(c, p, 1, i, i + 1, g));
     }
     // upsample.0 (at h x w): its input is LeakyReLU(point_conv) => mask with P
-    CK(c.conv_ps_dgrad(c.at(gu0), p.up_wd[0], c.at(gp), c.at(p.Pt[i]), MASK_LEAKY, n, h, w, p.sb ? c.at(p.SBPt[i]) : nullptr, p.unsh, false));
+    CK(c.conv_ps_dgrad(c.at(gu0), c.at(p.up_wd[0]), c.at(gp), c.at(p.Pt[i]), MASK_LEAKY, n, h, w, p.sb ? c.at(p.SBPt[i]) : nullptr, p.unsh, false));
     if (!p.hrdef) CK(recon_ps_wgrads(c, p, 0, i, i + 1, g));
     {   // point_conv dgrad: two 64-channel outputs (d outputs[i], d feat_prop)
-        ConvArgs a = c.base(n, h, w);
+        ConvArgs a = conv_args(n, h, w, c.C);
         a.src[0] = c.at(gp); a.wpack = c.at(p.point_wd); a.w_zstride = p.CO * C; a.nz = 2;
         a.dst[0] = c.at(p.dFeatB[i]); a.dst[1] = c.at(p.dFF[i]);
         CK(vsr_launch_conv(c.dtype, 1, 1, C, C, 0, p.CO, EPI_NHWC, a, c.st));
@@ -940,16 +951,16 @@ int trunk_backward(const Ctx& c, const Plan& p, int dir, int i, const void* dtop
     for (int b = chain ? 0 : rb - 1; b >= 0; --b) {
         const void* dxn = c.at(p.dxoff(dir, i, b + 1));
         // dA = dgrad(conv2)(dX_{b+1}) * ReLU'(A_b)
-        if (!chain) CK(c.conv64(dxn, p.blk_wd[dir][2 * b + 1], nullptr, c.at(p.g1off(dir, i, b)), ACT_NONE, nullptr, c.at(p.aoff(dir, i, b)), MASK_RELU, n, h, w,
+        if (!chain) CK(c.conv(3, dxn, c.at(p.blk_wd[dir][2 * b + 1]), nullptr, c.at(p.g1off(dir, i, b)), ACT_NONE, nullptr, c.at(p.aoff(dir, i, b)), MASK_RELU, n, h, w,
                     nullptr, p.sb ? c.at(p.sboff(dir, i, b)) : nullptr));
         // dX_b = dX_{b+1} + dgrad(conv1)(dA); for b == 0 also through the stem's LeakyReLU
         void* out = b > 0 ? c.at(p.dxoff(dir, i, b)) : c.at(p.G0[dir][i]);
-        CK(c.conv64(c.at(p.g1off(dir, i, b)), p.blk_wd[dir][2 * b], nullptr, out, ACT_NONE, dxn, b == 0 ? c.at(p.xoff(dir, i, 0)) : nullptr,
+        CK(c.conv(3, c.at(p.g1off(dir, i, b)), c.at(p.blk_wd[dir][2 * b]), nullptr, out, ACT_NONE, dxn, b == 0 ? c.at(p.xoff(dir, i, 0)) : nullptr,
                     b == 0 ? MASK_LEAKY : 0, n, h, w, nullptr, (b == 0 && p.sb) ? c.at(p.SBX0[dir][i]) : nullptr));
         if (p.diet) CK(block_wgrads(c, p, dir, b, i, i + 1, g));
     }
     if (has_warp)   // gradient w.r.t. the warped state (feat part of the stem's input)
-        CK(c.conv64(c.at(p.G0[dir][i]), p.stem_wd[dir], nullptr, c.at(p.dWp[dir]), ACT_NONE, nullptr, nullptr, 0, n, h, w));
+        CK(c.conv(3, c.at(p.G0[dir][i]), c.at(p.stem_wd[dir]), nullptr, c.at(p.dWp[dir]), ACT_NONE, nullptr, nullptr, 0, n, h, w));
     if (p.diet) CK(stem_wgrads(c, p, dir, i, i + 1, lrs, g));
     return VSR_OK;
 }
@@ -957,30 +968,20 @@ int trunk_backward(const Ctx& c, const Plan& p, int dir, int i, const void* dtop
 // Weight gradients of one direction's trunk for the frames [f0, f1) (at most VSR_WG_MAXSEG per launch): the stem ...
 int stem_wgrads(const Ctx& c, const Plan& p, int dir, int f0, int f1, const float* lrs, float* const* g) {
     const PIdx ix{p.rb, p.ups};
-    const WG wg{c};
     const int n = p.n, t = p.t, h = p.h, w = p.w, C = p.C;
-    {   // LR part (+ bias)
-        WgradArgs a = wg_base(n, h, w, C, C);
-        a.nseg = 0;
-        for (int i = f0; i < f1; ++i) { a.x[a.nseg] = lrs + (size_t)i * 3 * h * w; a.dy[a.nseg] = c.at(p.G0[dir][i]); ++a.nseg; }
-        a.x_nstride = (long long)t * 3 * h * w;
-        CK(wg.run(3, 16, true, C, false, a, C, 3, g[ix.stem_w(dir)], C + 3, 0, 1, 0, g[ix.stem_b(dir)]));
+    WgradArgs a = wg_base(n, h, w, C, C), af = a;      // LR part (+ bias); feat part: only frames that had a warped state
+    a.nseg = af.nseg = 0;
+    a.x_nstride = (long long)t * 3 * h * w;
+    for (int i = f0; i < f1; ++i) {
+        a.x[a.nseg] = lrs + (size_t)i * 3 * h * w; a.dy[a.nseg] = c.at(p.G0[dir][i]); ++a.nseg;
+        const bool has = dir == 0 ? (i < t - 1) : (i > 0);
+        if (has) { af.x[af.nseg] = c.at(p.Wp[dir][i]); af.dy[af.nseg] = c.at(p.G0[dir][i]); ++af.nseg; }
     }
-    {   // feat part: only frames that had a warped state
-        WgradArgs a = wg_base(n, h, w, C, C);
-        a.nseg = 0;
-        for (int i = f0; i < f1; ++i) {
-            const bool has = dir == 0 ? (i < t - 1) : (i > 0);
-            if (has) { a.x[a.nseg] = c.at(p.Wp[dir][i]); a.dy[a.nseg] = c.at(p.G0[dir][i]); ++a.nseg; }
-        }
-        if (a.nseg) CK(wg.run(3, C, false, C, false, a, C, C, g[ix.stem_w(dir)], C + 3, 3, 1, 0, nullptr));
-    }
-    return VSR_OK;
+    return c.stem_wgrads(true, a, af, g[ix.stem_w(dir)], g[ix.stem_b(dir)], 1);
 }
 // ... and the two convs of ResidualConv block b
 int block_wgrads(const Ctx& c, const Plan& p, int dir, int b, int f0, int f1, float* const* g) {
     const PIdx ix{p.rb, p.ups};
-    const WG wg{c};
     const int C = p.C;
     WgradArgs a1 = wg_base(p.n, p.h, p.w, C, C), a2 = wg_base(p.n, p.h, p.w, C, C);
     a1.nseg = a2.nseg = 0;
@@ -988,8 +989,8 @@ int block_wgrads(const Ctx& c, const Plan& p, int dir, int b, int f0, int f1, fl
         a1.x[a1.nseg] = c.at(p.xoff(dir, i, b)); a1.dy[a1.nseg] = c.at(p.g1off(dir, i, b)); ++a1.nseg;
         a2.x[a2.nseg] = c.at(p.aoff(dir, i, b)); a2.dy[a2.nseg] = c.at(p.dxoff(dir, i, b + 1)); ++a2.nseg;
     }
-    CK(wg.run(3, C, false, C, false, a1, C, C, g[ix.blk_w(dir, 2 * b)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b)]));
-    CK(wg.run(3, C, false, C, false, a2, C, C, g[ix.blk_w(dir, 2 * b + 1)], C, 0, 1, 0, g[ix.blk_b(dir, 2 * b + 1)]));
+    CK(c.wgrad_cc(3, a1, g[ix.blk_w(dir, 2 * b)], C, 0, g[ix.blk_b(dir, 2 * b)], 1));
+    CK(c.wgrad_cc(3, a2, g[ix.blk_w(dir, 2 * b + 1)], C, 0, g[ix.blk_b(dir, 2 * b + 1)], 1));
     return VSR_OK;
 }
 int trunk_wgrads(const Ctx& c, const Plan& p, int dir, const float* lrs, float* const* g) {
@@ -1030,7 +1031,7 @@ int backward_chain(const Ctx& c, const Plan& p, int dir, const float* lrs, float
 
 int backward_impl(const Plan& p, const float* const* prm, float* const* g, const float* lrs, const float* dsr, float* dlrs,
                   char* ws, hipStream_t st) {
-    const Ctx c{p, ws, st, p.dtype, 0};
+    const Ctx c = engine_ctx(p, ws, st, 0);
     // input gradient, part 1: the bilinear x4 skip (basicvsr.py:22,82) -- overwrites dlrs, everything else accumulates
     if (dlrs) CK(vsr_launch_bilinear4_bwd(dsr, dlrs, (long long)p.n * p.t * 3, p.h, p.w, st, p.scale));
     for (int i = p.t - 1; i >= 0; --i) CK(recon_backward(c, p, i, lrs, dsr, g, prm ? prm[PIdx{p.rb, p.ups}.last2_w()] : nullptr));   // -> dFeatB[i], dFF[i]
@@ -1043,18 +1044,15 @@ int backward_impl(const Plan& p, const float* const* prm, float* const* g, const
     // One stream: the two directions share their activation-gradient buffers (Plan::build), and chain launches of two streams could
     // each hold the CUs the other's unstarted workgroups need (conv3x3_chain.hip).  diet: rings per direction, no chains: two streams.
     CK(f.begin(p.diet));
-    const Ctx c0{p, ws, st, p.dtype, 0}, c1{p, ws, f.side(), p.dtype, 1};
+    const Ctx c0 = engine_ctx(p, ws, st, 0), c1 = engine_ctx(p, ws, f.side(), 1);
     CK(backward_chain(c0, p, 1, lrs, g));
     CK(backward_chain(c1, p, 0, lrs, g));
     CK(f.end());
     if (dlrs) {   // part 2: the stems' LR channels (conv.py:97 on cat([lr_i, feat])), both directions, every frame
         for (int dir = 0; dir < 2; ++dir)
             for (int i = 0; i < p.t; ++i) {
-                ConvArgs a = c.base(p.n, p.h, p.w);
-                a.src[0] = c.at(p.G0[dir][i]); a.wpack = c.at(p.stem_wd_lr[dir]); a.cout_real = 3;
                 float* d = dlrs + (size_t)i * 3 * p.h * p.w;
-                a.dst[0] = d; a.pres = d; a.dst_nstride = (long long)p.t * 3 * p.h * p.w;
-                CK(vsr_launch_conv(c.dtype, 3, 1, p.C, p.C, 0, 32, EPI_PLANAR, a, c.st));
+                CK(c.conv_planar3(c.at(p.G0[dir][i]), c.at(p.stem_wd_lr[dir]), nullptr, d, (long long)p.t * 3 * p.h * p.w, d, p.n, p.h, p.w));
             }
     }
     if (p.flowgrad && p.t > 1)   // part 3 (and train_flow): through the flows into SPyNet's parameters / image pyramid
@@ -1161,42 +1159,59 @@ int vsr_basicvsr_narrow_get_flows(const VsrBasicVSRDesc* d, const void* workspac
 }
 
 // ---- SPyNet alone ---------------------------------------------------------------------------------
-struct SpyAlone { SpyPlan sp; size_t frames, slab, dframes; size_t total; };
+struct SpyAlone { SpyPlan sp; size_t frames = 0, slab = 0, dframes = 0, total = 0; };
 static SpyAlone spy_alone_plan(int N, int h, int w, int dtype, bool save) {
     SpyAlone s; Bump b;
     s.frames = b.take((size_t)2 * N * 3 * h * w * 4);
     s.sp.plan(b, N, 2 * N, h, w, dtype);
-    s.slab = 0;
     if (save) {                                  // appended: the forward-only offsets do not move
         s.sp.plan_save(b, dtype);
-        int cp, xp, stride;
-        vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-        s.slab = b.take((size_t)VSR_WGRAD_NWG * stride * 4);
+        s.slab = b.take(wgrad_slab_bytes());
         s.dframes = b.take((size_t)2 * N * 3 * h * w * 4);
     }
     s.total = b.off;
     return s;
 }
+// the stand-alone forward / backward behind the four entries below (each entry checks its own arguments first)
+static int spy_alone_forward(int N, int h, int w, int dtype, const float* const* params, const float* ref, const float* supp, float* flow,
+                             bool last_relu, float* const* level_out, void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
+    if (bad_dtype(dtype)) return VSR_ERR_BADARG;
+    const SpyAlone s = spy_alone_plan(N, h, w, dtype, need_backward != 0);
+    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Ctx c((char*)workspace, st, dtype);
+    const size_t fb = (size_t)N * 3 * h * w * 4;
+    HIP_CHECK_RET(hipMemcpyAsync(c.at(s.frames), ref, fb, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK_RET(hipMemcpyAsync((char*)c.at(s.frames) + fb, supp, fb, hipMemcpyDeviceToDevice, st));
+    CK(spynet_pack(c, s.sp, params, 0));
+    return spynet_run(c, s.sp, c.fat(s.frames), params[60], params[61], N, 2, 1, flow, last_relu, level_out);
+}
+static int spy_alone_backward(int N, int h, int w, int dtype, float* const* grads, const float* dflow, const float* std, bool last_relu,
+                              const float* const* dlevel, float* dref, float* dsupp, void* workspace, size_t workspace_bytes, void* stream) {
+    if (bad_dtype(dtype)) return VSR_ERR_BADARG;
+    if (grads) for (int k = 0; k < 60; k += 2) if (!grads[k] && grads[k + 1]) return VSR_ERR_BADARG;   // a bias gradient comes with its weight's
+    const SpyAlone s = spy_alone_plan(N, h, w, dtype, true);
+    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const Ctx c((char*)workspace, st, dtype, 64, (float*)((char*)workspace + s.slab));
+    const bool want = dref || dsupp;
+    const size_t fb = (size_t)N * 3 * h * w * 4;
+    if (want) HIP_CHECK_RET(hipMemsetAsync(c.at(s.dframes), 0, 2 * fb, st));
+    CK(spynet_backward(c, s.sp, dflow, N, 2, 1, grads, 0, want ? (float*)c.at(s.dframes) : nullptr, std, last_relu, dlevel));
+    if (dref) HIP_CHECK_RET(hipMemcpyAsync(dref, c.at(s.dframes), fb, hipMemcpyDeviceToDevice, st));
+    if (dsupp) HIP_CHECK_RET(hipMemcpyAsync(dsupp, (char*)c.at(s.dframes) + fb, fb, hipMemcpyDeviceToDevice, st));
+    return VSR_OK;
+}
 
 size_t vsr_spynet_workspace_bytes(int N, int h, int w, int dtype, int need_backward) {
-    if (N < 1 || h < 1 || w < 1) return 0;
+    if (bad_dims(N, h, w)) return 0;
     return spy_alone_plan(N, h, w, dtype, need_backward != 0).total;
 }
 
 int vsr_spynet_forward(int N, int h, int w, int dtype, const float* const* params, int nparams, const float* ref,
                        const float* supp, float* flow, void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
     if (N < 1 || h < 1 || w < 1 || !params || nparams != 62 || !ref || !supp || !flow || !workspace) return VSR_ERR_BADARG;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, need_backward != 0);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype);
-    const Ctx c{dummy, (char*)workspace, st, dtype};
-    const size_t fb = (size_t)N * 3 * h * w * 4;
-    HIP_CHECK_RET(hipMemcpyAsync(c.at(s.frames), ref, fb, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK_RET(hipMemcpyAsync((char*)c.at(s.frames) + fb, supp, fb, hipMemcpyDeviceToDevice, st));
-    CK(spynet_pack(c, s.sp, params, 0));
-    return spynet_run(c, s.sp, c.fat(s.frames), params[60], params[61], N, 2, 1, flow);
+    return spy_alone_forward(N, h, w, dtype, params, ref, supp, flow, true, nullptr, workspace, workspace_bytes, need_backward, stream);
 }
 
 /* SPyNet with the options of the reference's OTHER SpyNet classes: last_relu = 0 is the canonical network
@@ -1206,29 +1221,13 @@ int vsr_spynet_forward_ex(int N, int h, int w, int dtype, const float* const* pa
                           const float* supp, int last_relu, float* const* level_out, void* workspace, size_t workspace_bytes,
                           int need_backward, void* stream) {
     if (N < 1 || h < 32 || w < 32 || !params || nparams != 62 || !ref || !supp || !level_out || !workspace) return VSR_ERR_BADARG;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, need_backward != 0);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype);
-    const Ctx c{dummy, (char*)workspace, st, dtype};
-    const size_t fb = (size_t)N * 3 * h * w * 4;
-    HIP_CHECK_RET(hipMemcpyAsync(c.at(s.frames), ref, fb, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK_RET(hipMemcpyAsync((char*)c.at(s.frames) + fb, supp, fb, hipMemcpyDeviceToDevice, st));
-    CK(spynet_pack(c, s.sp, params, 0));
-    return spynet_run(c, s.sp, c.fat(s.frames), params[60], params[61], N, 2, 1, nullptr, last_relu != 0, level_out);
+    return spy_alone_forward(N, h, w, dtype, params, ref, supp, nullptr, last_relu != 0, level_out, workspace, workspace_bytes, need_backward, stream);
 }
 
 int vsr_spynet_backward(int N, int h, int w, int dtype, float* const* grads, int nparams, const float* dflow, void* workspace,
                         size_t workspace_bytes, void* stream) {
     if (N < 1 || h < 1 || w < 1 || !grads || nparams != 62 || !dflow || !workspace) return VSR_ERR_BADARG;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    for (int k = 0; k < 60; k += 2) if (!grads[k] && grads[k + 1]) return VSR_ERR_BADARG;   // a bias gradient comes with its weight's
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, true);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    Plan dummy; dummy.es = esize(dtype); dummy.slab[0] = dummy.slab[1] = s.slab;
-    const Ctx c{dummy, (char*)workspace, (hipStream_t)stream, dtype};
-    return spynet_backward(c, s.sp, dflow, N, 2, 1, grads, 0);
+    return spy_alone_backward(N, h, w, dtype, grads, dflow, nullptr, true, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 /* the same, plus the gradient w.r.t. the two input frames: dref, dsupp (N,3,h,w) fp32 are WRITTEN (either may be NULL).
@@ -1240,31 +1239,18 @@ int vsr_spynet_backward_ex(int N, int h, int w, int dtype, const float* const* p
     bool any = dflow != nullptr;
     if (dlevel) for (int l = 0; l < 6; ++l) any = any || dlevel[l];
     if (!any) return VSR_ERR_BADARG;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    if (grads) for (int k = 0; k < 60; k += 2) if (!grads[k] && grads[k + 1]) return VSR_ERR_BADARG;
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, true);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype); dummy.slab[0] = dummy.slab[1] = s.slab;
-    const Ctx c{dummy, (char*)workspace, st, dtype};
-    const bool want = dref || dsupp;
-    const size_t fb = (size_t)N * 3 * h * w * 4;
-    if (want) HIP_CHECK_RET(hipMemsetAsync(c.at(s.dframes), 0, 2 * fb, st));
-    CK(spynet_backward(c, s.sp, dflow, N, 2, 1, grads, 0, want ? (float*)c.at(s.dframes) : nullptr, params[61], last_relu != 0, dlevel));
-    if (dref) HIP_CHECK_RET(hipMemcpyAsync(dref, c.at(s.dframes), fb, hipMemcpyDeviceToDevice, st));
-    if (dsupp) HIP_CHECK_RET(hipMemcpyAsync(dsupp, (char*)c.at(s.dframes) + fb, fb, hipMemcpyDeviceToDevice, st));
-    return VSR_OK;
+    return spy_alone_backward(N, h, w, dtype, grads, dflow, params[61], last_relu != 0, dlevel, dref, dsupp, workspace, workspace_bytes, stream);
 }
 
 // ---- RealBasicVSR pre-clean stack, forward (realbasicvsr.py:17-30) ------------------------------------
 // x <- x + conv(ResidualBlock(x)), `steps` times, on the F = n*t frames of the clip.
 // params: resblock.conv.0.{weight,bias}, resblock.res_block.{i}.conv{1,2}.{weight,bias} ..., conv.{weight,bias}
 struct CleanPlan {
-    size_t stem_w, stem_b, out_w, out_b, feat, act, xa, xb, total;
+    size_t stem_w = 0, stem_b = 0, out_w = 0, out_b = 0, feat = 0, act = 0, xa = 0, xb = 0, total = 0;
     std::vector<size_t> blk_w, blk_b;
     // need_backward: data-gradient weights, per-step saved tensors, backward scratch
     bool save = false;
-    size_t stem_wd, out_wd, slab, dXa, dXb, dA, G0, dxa, dxb;
+    size_t stem_wd = 0, out_wd = 0, slab = 0, dXa = 0, dXb = 0, dA = 0, G0 = 0, dxa = 0, dxb = 0;
     std::vector<size_t> blk_wd;
     std::vector<size_t> xs;             // [steps]: planar fp32 input of each step (xs[0] unused: the caller's lr)
     std::vector<size_t> X, A;           // [steps][blocks+1] / [steps][blocks]
@@ -1287,9 +1273,7 @@ static CleanPlan clean_plan(int F, int h, int w, int blocks, int dtype, int step
         p.stem_wd = b.take((size_t)9 * 32 * C * es); p.out_wd = b.take((size_t)9 * CO * 16 * es);
         p.blk_wd.resize(2 * blocks);
         for (int k = 0; k < 2 * blocks; ++k) p.blk_wd[k] = b.take(w64);
-        int cp, xp, stride;
-        vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-        p.slab = b.take((size_t)VSR_WGRAD_NWG * stride * 4);
+        p.slab = b.take(wgrad_slab_bytes());
         p.dXa = b.take(a1); p.dXb = b.take(a1); p.dA = b.take(a1); p.G0 = b.take(a1);
         p.dxa = b.take(x1); p.dxb = b.take(x1);
         p.xs.assign(steps, 0); p.X.assign((size_t)steps * (blocks + 1), 0); p.A.assign((size_t)steps * blocks, 0);
@@ -1320,49 +1304,39 @@ int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int s
                         void* stream) {
     if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !params || !lr || !lq || !workspace) return VSR_ERR_BADARG;
     if (!cleaner_width_ok(mid_channels)) return VSR_ERR_UNSUPPORTED;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    if (nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
+    if (bad_dtype(dtype) || nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
     const bool save = need_backward != 0;
-    const int C = mid_channels, CO = C < 32 ? 32 : C;
+    const int C = mid_channels;
     const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, save, C);
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype); dummy.C = C; dummy.CO = CO;
-    const Ctx c{dummy, (char*)workspace, st, dtype};
-    CK(c.pack(params[0], p.stem_w, 9, CO, 16, C, 3, 3, 0, 1, 0, 0));
-    CK(c.pack_bias(params[1], p.stem_b, C));
+    const Ctx c((char*)workspace, (hipStream_t)stream, dtype, C);
+    const int CO = c.CO;
+    CK(c.pack_stem(params[0], c.at(p.stem_w), false));
+    CK(c.pack_bias(params[1], c.at(p.stem_b), C));
     for (int k = 0; k < 2 * blocks; ++k) {
-        CK(c.pack(params[2 + 2 * k], p.blk_w[k], 9, CO, C, C, C, C, 0, 1, 0, 0));
-        CK(c.pack_bias(params[3 + 2 * k], p.blk_b[k], C));
-        if (save) CK(c.pack(params[2 + 2 * k], p.blk_wd[k], 9, CO, C, C, C, C, 0, 1, 0, 1));
+        CK(c.pack_cc(3, params[2 + 2 * k], c.at(p.blk_w[k]), 0));
+        CK(c.pack_bias(params[3 + 2 * k], c.at(p.blk_b[k]), C));
+        if (save) CK(c.pack_cc(3, params[2 + 2 * k], c.at(p.blk_wd[k]), 1));
     }
-    CK(c.pack(params[2 + 4 * blocks], p.out_w, 9, 32, C, 3, C, C, 0, 1, 0, 0));
-    CK(c.pack_bias(params[3 + 4 * blocks], p.out_b, 3));
+    CK(c.pack(params[2 + 4 * blocks], c.at(p.out_w), 9, 32, C, 3, C, C, 0, 1, 0, 0));
+    CK(c.pack_bias(params[3 + 4 * blocks], c.at(p.out_b), 3));
     if (save) {
-        CK(c.pack(params[0], p.stem_wd, 9, 32, C, 3, C, 3, 0, 1, 0, 1));                  // C -> 3 (planar epilogue)
-        CK(c.pack(params[2 + 4 * blocks], p.out_wd, 9, CO, 16, C, 3, C, 0, 1, 0, 1));     // 3 (planar source) -> C
+        CK(c.pack_stem_dlr(params[0], c.at(p.stem_wd), false));                            // C -> 3 (planar epilogue)
+        CK(c.pack(params[2 + 4 * blocks], c.at(p.out_wd), 9, CO, 16, C, 3, C, 0, 1, 0, 1));     // 3 (planar source) -> C
     }
     const float* xin = lr;
     for (int s = 0; s < steps; ++s) {
         float* xout = (s == steps - 1) ? lq : (float*)c.at(save ? p.xs[s + 1] : ((s & 1) ? p.xb : p.xa));
         auto Xs = [&](int k) { return save ? c.at(p.X[(size_t)s * (blocks + 1) + k]) : c.at(p.feat); };
-        {   // ResidualBlock stem: conv3x3 3->64 + LeakyReLU(0.1) on the planar frames (conv.py:97)
-            ConvArgs a = c.base(F, h, w);
-            a.src[0] = xin; a.src_nstride[0] = (long long)3 * h * w;
-            a.wpack = c.at(p.stem_w); a.bias = c.fat(p.stem_b); a.dst[0] = Xs(0); a.act = ACT_LEAKY;
-            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st));
-        }
+        // ResidualBlock stem: conv3x3 3->64 + LeakyReLU(0.1) on the planar frames (conv.py:97)
+        CK(c.stem(false, nullptr, xin, (long long)3 * h * w, c.at(p.stem_w), c.fat(p.stem_b), Xs(0), ACT_LEAKY, 0.f, F, h, w));
         for (int b = 0; b < blocks; ++b) {
             void* act = save ? c.at(p.A[(size_t)s * blocks + b]) : c.at(p.act);
-            CK(c.conv64(Xs(b), p.blk_w[2 * b], c.fat(p.blk_b[2 * b]), act, ACT_RELU, nullptr, nullptr, 0, F, h, w));
-            CK(c.conv64(act, p.blk_w[2 * b + 1], c.fat(p.blk_b[2 * b + 1]), Xs(b + 1), ACT_NONE, Xs(b), nullptr, 0, F, h, w));
+            CK(c.conv(3, Xs(b), c.at(p.blk_w[2 * b]), c.fat(p.blk_b[2 * b]), act, ACT_RELU, nullptr, nullptr, 0, F, h, w));
+            CK(c.conv(3, act, c.at(p.blk_w[2 * b + 1]), c.fat(p.blk_b[2 * b + 1]), Xs(b + 1), ACT_NONE, Xs(b), nullptr, 0, F, h, w));
         }
-        {   // x + conv3x3 64->3 (realbasicvsr.py:28-29; a fresh tensor instead of the reference's in-place +=)
-            ConvArgs a = c.base(F, h, w);
-            a.src[0] = Xs(blocks); a.wpack = c.at(p.out_w); a.bias = c.fat(p.out_b); a.cout_real = 3;
-            a.dst[0] = xout; a.dst_nstride = (long long)3 * h * w; a.pres = xin;
-            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
-        }
+        // x + conv3x3 64->3 (realbasicvsr.py:28-29; a fresh tensor instead of the reference's in-place +=)
+        CK(c.conv_planar3(Xs(blocks), c.at(p.out_w), c.fat(p.out_b), xout, (long long)3 * h * w, xin, F, h, w));
         xin = xout;
     }
     return VSR_OK;
@@ -1375,15 +1349,11 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
                          const float* lr, const float* dlq, float* dlr, void* workspace, size_t workspace_bytes, void* stream) {
     if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !grads || !lr || !dlq || !workspace) return VSR_ERR_BADARG;
     if (!cleaner_width_ok(mid_channels) || blocks < 1) return VSR_ERR_UNSUPPORTED;      // the stem's LeakyReLU mask is fused into block 0's dgrad
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
-    if (nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
-    const int C = mid_channels, CO = C < 32 ? 32 : C;
+    if (bad_dtype(dtype) || nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
+    const int C = mid_channels;
     const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, true, C);
     if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    Plan dummy; dummy.es = esize(dtype); dummy.slab[0] = dummy.slab[1] = p.slab; dummy.C = C; dummy.CO = CO;
-    const Ctx c{dummy, (char*)workspace, st, dtype};
-    const WG wg{c};
+    const Ctx c((char*)workspace, (hipStream_t)stream, dtype, C, (float*)((char*)workspace + p.slab));
     const float* dx = dlq;                                   // gradient w.r.t. x_{s+1}
     for (int s = steps - 1; s >= 0; --s) {
         const float* xs = s == 0 ? lr : c.fat(p.xs[s]);
@@ -1393,28 +1363,25 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
         {   // out conv C->3: X = X_blocks, dY = dx (planar)
             WgradArgs a = wg_base(F, h, w, C, C);
             a.x[0] = Xs(blocks); a.dy[0] = dx; a.dy_nstride = (long long)3 * h * w;
-            CK(wg.run(3, C, false, 16, true, a, 3, C, gow, C, 0, 1, 0, gob));
+            CK(c.wgrad(a, {3, C, false, 16, true}, {3, C, gow, C, 0, 1, 0, gob, 1}));
         }
         size_t dcur = p.dXa, dnext = p.dXb;
-        {   // d X_blocks = dgrad(out conv)(dx)
-            ConvArgs a = c.base(F, h, w);
-            a.src[0] = dx; a.src_nstride[0] = (long long)3 * h * w; a.wpack = c.at(p.out_wd); a.dst[0] = c.at(dcur);
-            CK(vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st));
-        }
+        // d X_blocks = dgrad(out conv)(dx): planar 3 -> C, the stem's launch on the flipped weights
+        CK(c.stem(false, nullptr, dx, (long long)3 * h * w, c.at(p.out_wd), nullptr, c.at(dcur), ACT_NONE, 0.f, F, h, w));
         for (int b = blocks - 1; b >= 0; --b) {   // x + conv2(relu(conv1(x)))   (conv.py:89-92)
-            CK(c.conv64(c.at(dcur), p.blk_wd[2 * b + 1], nullptr, c.at(p.dA), ACT_NONE, nullptr, As(b), MASK_RELU, F, h, w));
+            CK(c.conv(3, c.at(dcur), c.at(p.blk_wd[2 * b + 1]), nullptr, c.at(p.dA), ACT_NONE, nullptr, As(b), MASK_RELU, F, h, w));
             {
                 WgradArgs a = wg_base(F, h, w, C, C);
                 a.x[0] = As(b); a.dy[0] = c.at(dcur);
-                CK(wg.run(3, C, false, C, false, a, C, C, grads[2 + 2 * (2 * b + 1)], C, 0, 1, 0, grads[3 + 2 * (2 * b + 1)]));
+                CK(c.wgrad_cc(3, a, grads[2 + 2 * (2 * b + 1)], C, 0, grads[3 + 2 * (2 * b + 1)], 1));
             }
             void* out = b > 0 ? c.at(dnext) : c.at(p.G0);      // b == 0: also through the stem's LeakyReLU
-            CK(c.conv64(c.at(p.dA), p.blk_wd[2 * b], nullptr, out, ACT_NONE, c.at(dcur), b == 0 ? Xs(0) : nullptr,
+            CK(c.conv(3, c.at(p.dA), c.at(p.blk_wd[2 * b]), nullptr, out, ACT_NONE, c.at(dcur), b == 0 ? Xs(0) : nullptr,
                         b == 0 ? MASK_LEAKY : 0, F, h, w));
             {
                 WgradArgs a = wg_base(F, h, w, C, C);
                 a.x[0] = Xs(b); a.dy[0] = c.at(p.dA);
-                CK(wg.run(3, C, false, C, false, a, C, C, grads[2 + 2 * (2 * b)], C, 0, 1, 0, grads[3 + 2 * (2 * b)]));
+                CK(c.wgrad_cc(3, a, grads[2 + 2 * (2 * b)], C, 0, grads[3 + 2 * (2 * b)], 1));
             }
             const size_t tmp = dcur; dcur = dnext; dnext = tmp;
         }
@@ -1422,15 +1389,12 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
         {   // stem 3->C: X = x_s (planar), dY = G0
             WgradArgs a = wg_base(F, h, w, C, C);
             a.x[0] = xs; a.x_nstride = (long long)3 * h * w; a.dy[0] = g0;
-            CK(wg.run(3, 16, true, C, false, a, C, 3, grads[0], 3, 0, 1, 0, grads[1]));
+            CK(c.stem_wgrads(false, a, a, grads[0], grads[1], 1));
         }
         const bool last = s == 0;
         if (!last || dlr) {   // d x_s = d x_{s+1} + dgrad(stem)(G0)
             float* dxs = last ? dlr : (float*)c.at((s & 1) ? p.dxa : p.dxb);
-            ConvArgs a = c.base(F, h, w);
-            a.src[0] = g0; a.wpack = c.at(p.stem_wd); a.cout_real = 3;
-            a.dst[0] = dxs; a.dst_nstride = (long long)3 * h * w; a.pres = dx;
-            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
+            CK(c.conv_planar3(g0, c.at(p.stem_wd), nullptr, dxs, (long long)3 * h * w, dx, F, h, w));
             dx = dxs;
         }
     }
@@ -1438,22 +1402,17 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
 }
 
 // ---- per-op entry points -------------------------------------------------------------------------
-static bool bad_dtype(int dtype) { return dtype != VSR_F32 && dtype != VSR_BF16; }
 static bool layer_width_ok(int c) { return c == 16 || c == 32 || c == 64; }      // the widths of the per-op trunk / stem / shuffle layers
-static bool bad_dims(int N, int H, int W) { return N < 1 || H < 1 || W < 1; }
 
 int vsr_flow_warp_fwd(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !in_pm || !flow || !out_pm || bad_dims(N, H, W) || Cc < 16 || (Cc & 15)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_fwd(dtype, in_pm, flow, out_pm, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_flow_warp_fwd_ex(dtype, in_pm, flow, out_pm, N, H, W, Cc, 0, stream);
 }
 int vsr_flow_warp_bwd(int dtype, const void* dout_pm, const float* flow, float* dacc, int N, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !dacc || bad_dims(N, H, W) || Cc < 16 || (Cc & 15)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd(dtype, dout_pm, flow, dacc, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_flow_warp_bwd_ex(dtype, dout_pm, flow, dacc, N, H, W, Cc, 0, stream);
 }
 int vsr_flow_warp_bwd_flow(int dtype, const void* in_pm, const void* dout_pm, const float* flow, float* dflow, int N, int H, int W,
                            int Cc, void* stream) {
-    if (bad_dtype(dtype) || !in_pm || !dout_pm || !flow || !dflow || bad_dims(N, H, W) || Cc < 16 || (Cc & 15)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_flow(dtype, in_pm, dout_pm, flow, dflow, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_flow_warp_bwd_flow_ex(dtype, in_pm, dout_pm, flow, dflow, N, H, W, Cc, 0, stream);
 }
 /* padding_mode: 0 = 'zeros' (the propagation warps), 1 = 'border' (the warps inside SPyNet, spynet.py:60) */
 int vsr_flow_warp_fwd_ex(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H, int W, int Cc, int padding_mode,
@@ -1494,22 +1453,12 @@ int vsr_pm_to_planar(int dtype, const void* in_pm, float* out, int N, int Cout, 
     return vsr_launch_pm_to_planar(dtype, in_pm, out, N, Cout, H, W, Cc, (hipStream_t)stream);
 }
 
-static ConvArgs plain64(const void* x, const void* wpack, const float* b, void* y, int N, int H, int W, int C = 64) {
-    ConvArgs a = {};
-    a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1; a.out_step = 1; a.Hd = H; a.Wd = W; a.CD = C; a.cout_real = C;
-    a.dst_nstride = pm_image_elems(H, W, C); a.src_nstride[0] = pm_image_elems(H, W, C);
-    a.src[0] = x; a.wpack = wpack; a.bias = b; a.dst[0] = y;
-    return a;
-}
-
 int vsr_conv3x3_c64_fwd(int dtype, const void* x_pm, const float* w, const float* b, void* wpack, void* y_pm, const void* res_pm,
                         int act, int N, int H, int W, void* stream) {
     if (bad_dtype(dtype) || !x_pm || !wpack || !y_pm || bad_dims(N, H, W) || act < ACT_NONE || act > ACT_LEAKY) return VSR_ERR_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (w) CK(vsr_launch_pack_weights(dtype, w, wpack, 9, C, C, C, C, C, 0, 1, 0, 0, st));   // w == NULL: wpack already packed
-    ConvArgs a = plain64(x_pm, wpack, b, y_pm, N, H, W);
-    a.act = act; a.res[0] = res_pm;
-    return vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+    const Ctx c(nullptr, (hipStream_t)stream, dtype);
+    if (w) CK(c.pack_cc(3, w, wpack, 0));   // w == NULL: wpack already packed
+    return c.conv(3, x_pm, wpack, b, y_pm, act, res_pm, nullptr, 0, N, H, W);
 }
 
 size_t vsr_conv3x3_c64_chain_sync_bytes(int nlayers, int N, int H, int W) {
@@ -1550,11 +1499,9 @@ int vsr_conv3x3_c64_dgrad(int dtype, const void* dy_pm, const float* w, void* wp
     if (bad_dtype(dtype) || !dy_pm || !w || !wpack || !dx_pm || bad_dims(N, H, W) || mask_mode < MASK_NONE || mask_mode > MASK_LEAKY ||
         (mask_mode != MASK_NONE && !aux_pm))
         return VSR_ERR_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    CK(vsr_launch_pack_weights(dtype, w, wpack, 9, C, C, C, C, C, 0, 1, 0, 1, st));
-    ConvArgs a = plain64(dy_pm, wpack, nullptr, dx_pm, N, H, W);
-    a.res[0] = res_pm; a.aux[0] = aux_pm; a.mask_mode = mask_mode;
-    return vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
+    const Ctx c(nullptr, (hipStream_t)stream, dtype);
+    CK(c.pack_cc(3, w, wpack, 1));
+    return c.conv(3, dy_pm, wpack, nullptr, dx_pm, ACT_NONE, res_pm, aux_pm, mask_mode, N, H, W);
 }
 
 /* Backward of ONE conv layer of vsr_conv_layer_fwd (same shapes, same argument meaning): the reference's building blocks are ordinary
@@ -1570,9 +1517,7 @@ size_t vsr_conv_layer_bwd_scratch_bytes(int dtype, int N, int H, int W, int pixe
     if (bad_dtype(dtype) || bad_dims(N, H, W)) return 0;
     const size_t es = esize(dtype);
     const int s = pixel_shuffle ? 2 : 1;
-    int cp3, xp3, stride3;
-    vsr_wgrad_slab_dims(3, 64, 64, &cp3, &xp3, &stride3);
-    return (size_t)49 * 64 * 64 * 4 * es + (size_t)N * pm_image_elems(s * H, s * W, C) * es + (size_t)VSR_WGRAD_NWG * stride3 * 4 + 1024;
+    return (size_t)49 * 64 * 64 * 4 * es + (size_t)N * pm_image_elems(s * H, s * W, C) * es + wgrad_slab_bytes() + 1024;
 }
 
 int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const float* lr_planar, const float* w, int cin_real, int cout_real,
@@ -1592,24 +1537,6 @@ int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
     float* slab = reinterpret_cast<float*>(dym + (((size_t)N * pm_image_elems(sps * H, sps * W, C) * es + 255) & ~(size_t)255));
     const float mslope = act == ACT_LEAKY ? vsr_slope(slope) : 0.f;
 
-    // one weight-gradient launch + its reduction (gw / gb overwritten on the first call of a layer, accumulated by later ones)
-    auto wgrad = [&](int wks, int cx, bool xp, int cout, WgradArgs& a, int co_real, int ci_real, int I_total, int i_off, int o_mul, int o_add,
-                     float* gbias, int accumulate) -> int {
-        int cp, xpd, stride;
-        vsr_wgrad_slab_dims(wks, cx, cout, &cp, &xpd, &stride);
-        a.slab = slab; a.slab_stride = stride;
-        int cp3, xp3, stride3;
-        vsr_wgrad_slab_dims(3, 64, 64, &cp3, &xp3, &stride3);
-        const int tiles = a.N * cdiv(a.H, 8) * cdiv(a.W, 32);
-        const long long cap = (long long)VSR_WGRAD_NWG * stride3 / stride;
-        int nwg = tiles < VSR_WGRAD_NWG ? tiles : VSR_WGRAD_NWG;
-        if (nwg > cap) nwg = (int)cap;
-        if (nwg > 1) nwg &= ~1;
-        int nslabs = 0;
-        CK(vsr_launch_wgrad(dtype, wks, cx, xp, cout, false, a, nwg, &nslabs, st));
-        return vsr_launch_wgrad_reduce(slab, nslabs, wks, cx, cout, co_real, ci_real, gw, I_total, i_off, o_mul, o_add, gbias, accumulate, st);
-    };
-
     if (!dy_pm) {   // planar output: the 16 -> 2 SPyNet layer.  dyM as a 16-channel pixel-major tensor
         if (ks != 7 || cout_real != 2 || cin_pm != 16 || cin_real != 16 || !x_pm || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
         if (act == ACT_RELU) CK(vsr_launch_spynet_dres(dtype, dy_planar, y_planar, dym, N, H, W, st));
@@ -1621,102 +1548,63 @@ int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
     }
     const void* dyM = (!dy_pm || act != ACT_NONE) ? (const void*)dym : dy_pm;
 
+    // (gw / gb are overwritten: every reduction below writes its own part of them)
     if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone  (conv.py:97), C = 16, 32 or 64
-        const int C = cout_real, CO = C < 32 ? 32 : C;
+        const int C = cout_real;
         if (ks != 3 || !layer_width_ok(C) || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
         const bool cat = x_pm != nullptr;
         if ((cat && (cin_pm != C || cin_real != C + 3)) || (!cat && cin_real != 3)) return VSR_ERR_UNSUPPORTED;
-        const int I_total = cat ? C + 3 : 3;
+        const Ctx c(nullptr, st, dtype, C, slab);
         if (cat && dx_pm) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, C, C, C, I_total, 3, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
-            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st));
+            CK(c.pack_stem_dgrad(w, wp));
+            CK(c.conv(3, dyM, wp, nullptr, dx_pm, ACT_NONE, nullptr, nullptr, 0, N, H, W));
         }
         if (dlr_planar) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, 9, 32, C, 3, C, I_total, 0, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dlr_planar, N, H, W, C);
-            a.cout_real = 3; a.dst_nstride = (long long)3 * H * W;
-            CK(vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st));
+            CK(c.pack_stem_dlr(w, wp, cat));
+            CK(c.conv_planar3(dyM, wp, nullptr, dlr_planar, (long long)3 * H * W, nullptr, N, H, W));
         }
         if (gw) {
-            WgradArgs a = wg_base(N, H, W, C, C);
+            WgradArgs a = wg_base(N, H, W, C, C), af = a;
             a.x[0] = lr_planar; a.x_nstride = (long long)3 * H * W; a.dy[0] = dyM;
-            CK(wgrad(3, 16, true, C, a, C, 3, I_total, 0, 1, 0, gb, 0));
-            if (cat) {
-                WgradArgs b2 = wg_base(N, H, W, C, C);
-                b2.x[0] = x_pm; b2.dy[0] = dyM;
-                CK(wgrad(3, C, false, C, b2, C, C, I_total, 3, 1, 0, nullptr, 0));
-            }
+            af.x[0] = x_pm; af.dy[0] = dyM;
+            CK(c.stem_wgrads(cat, a, af, gw, gb, 0));
         }
         return VSR_OK;
     }
     if (ks == 3 || ks == 1) {
-        const int C = cin_pm, CO = C < 32 ? 32 : C;
+        const int C = cin_pm;
         if (!layer_width_ok(C) || cin_real != C || !x_pm) return VSR_ERR_UNSUPPORTED;
+        const Ctx c(nullptr, st, dtype, C, slab);
         if (pixel_shuffle) {                               // conv3x3 C -> 4C + PixelShuffle(2)  (upsampling.py:10-12)
             if (ks != 3 || cout_real != 4 * C || cd != C || act != ACT_NONE) return VSR_ERR_UNSUPPORTED;
             if (dx_pm) {
-                for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, 1, st));
-                if (dtype == VSR_BF16 && C == 64) {
-                    for (int z = 0; z < 4; ++z) {          // phase z reads phase z-1's partial sum as its residual, in place
-                        ConvArgs a = plain64(dyM, wp + (size_t)z * 9 * C * C * es, nullptr, dx_pm, N, H, W);
-                        a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W; a.src_oy[0] = z >> 1; a.src_ox[0] = z & 1;
-                        a.src_nstride[0] = pm_image_elems(2 * H, 2 * W, C);
-                        a.res[0] = z > 0 ? dx_pm : nullptr;
-                        CK(vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st));
-                    }
-                } else {
-                    ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
-                    a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
-                    for (int q = 0; q < 4; ++q) { a.src[q] = dyM; a.src_oy[q] = q >> 1; a.src_ox[q] = q & 1; a.src_nstride[q] = pm_image_elems(2 * H, 2 * W, C); }
-                    CK(vsr_launch_conv(dtype, 3, 4, C, C, 0, CO, EPI_NHWC, a, st));
-                }
+                CK(c.pack_ps(w, wp, 1));
+                CK(c.conv_ps_dgrad(dyM, wp, dx_pm, nullptr, 0, N, H, W));
             }
-            if (gw)
-                for (int z = 0; z < 4; ++z) {
-                    WgradArgs a = wg_base(N, H, W, C, C);
-                    a.x[0] = x_pm; a.dy[0] = dyM;
-                    a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C);
-                    CK(wgrad(3, C, false, C, a, C, C, C, 0, 4, z, gb, 0));
-                }
+            if (gw) CK(c.ps_wgrads(&x_pm, &dyM, 1, false, N, H, W, gw, gb, 0));
             return VSR_OK;
         }
         if (cout_real != C || cd != C) return VSR_ERR_UNSUPPORTED;
         if (dx_pm) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, CO, C, C, C, C, 0, 1, 0, 1, st));
-            ConvArgs a = plain64(dyM, wp, nullptr, dx_pm, N, H, W, C);
-            CK(vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st));
+            CK(c.pack_cc(ks, w, wp, 1));
+            CK(c.conv(ks, dyM, wp, nullptr, dx_pm, ACT_NONE, nullptr, nullptr, 0, N, H, W));
         }
         if (gw) {
             WgradArgs a = wg_base(N, H, W, C, C);
             a.x[0] = x_pm; a.dy[0] = dyM;
-            CK(wgrad(ks, C, false, C, a, C, C, C, 0, 1, 0, gb, 0));
+            CK(c.wgrad_cc(ks, a, gw, C, 0, gb, 0));
         }
         return VSR_OK;
     }
     if (ks != 7 || pixel_shuffle || !x_pm) return VSR_ERR_UNSUPPORTED;
     for (int j = 0; j < NSPY; ++j) {                       // the SPyNet layer shapes (spynet.py:16-18), as spynet_backward runs them
         if (cin_pm != SPY_CIP[j] || cout_real != SPY_CO[j] || cin_real != SPY_CI[j]) continue;
-        const int CI = SPY_CIP[j], CO = SPY_DK[j];
         if (j < NSPY - 1 && cd != SPY_CD[j]) return VSR_ERR_BADARG;
-        if (gw) {
-            const int nhalf = (dtype == VSR_F32 && CI == 64) ? 2 : 1;          // fp32, 64 input channels: two 32-channel halves (LDS)
-            for (int hf = 0; hf < nhalf; ++hf) {
-                WgradArgs a = wg_base(N, H, W);
-                a.x[0] = x_pm; a.x_nstride = pm_image_elems(H, W, CI);
-                a.dy[0] = dyM; a.dy_nstride = pm_image_elems(H, W, CO);
-                const int cx = CI / nhalf;
-                if (nhalf == 2) { a.x_ctotal = CI; a.x_coff = hf * (cx / 8); }
-                CK(wgrad(7, cx, false, CO, a, SPY_CO[j], nhalf == 2 ? cx : SPY_CI[j], SPY_CI[j], hf * cx, 1, 0, hf == 0 ? gb : nullptr, 0));
-            }
-        }
+        const Ctx c(nullptr, st, dtype, 64, slab);
+        if (gw) CK(c.spy_wgrad(j, x_pm, dyM, N, H, W, gw, gb, 0));
         if (dx_pm) {
-            CK(vsr_launch_pack_weights(dtype, w, wp, 49, SPY_DROWS[j], SPY_DK[j], SPY_CI[j], SPY_CO[j], SPY_CI[j], 0, 1, 0, 1, st));
-            ConvArgs a = {};
-            a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1; a.out_step = 1; a.Hd = H; a.Wd = W;
-            a.src[0] = dyM; a.src_nstride[0] = pm_image_elems(H, W, CO);
-            a.wpack = wp; a.dst[0] = dx_pm; a.CD = CI; a.cout_real = j == 0 ? 8 : CI; a.dst_nstride = pm_image_elems(H, W, CI);
-            CK(vsr_launch_conv(dtype, 7, 1, CO, CO, 0, SPY_DROWS[j], EPI_NHWC, a, st));
+            CK(c.pack_spy(j, w, wp, 1));
+            CK(c.spy_dgrad(j, dyM, wp, dx_pm, nullptr, N, H, W));
         }
         return VSR_OK;
     }
@@ -1737,89 +1625,52 @@ int vsr_conv_layer_fwd(int dtype, int ks, const void* x_pm, int cin_pm, const fl
     if (bad_dtype(dtype) || !w || !wpack || bad_dims(N, H, W) || (!x_pm && !lr_planar) || (!y_pm && !y_planar) || act < ACT_NONE || act > ACT_LEAKY)
         return VSR_ERR_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    const size_t es = esize(dtype);
-    float* bias = nullptr;
     char* wp = (char*)wpack;
-    if (b) {   // the kernels read the bias as fp32 from device memory: the caller's tensor is used as is (cout_real values, padded reads are masked by cout_real)
-        bias = const_cast<float*>(b);
-    }
-    ConvArgs a = {};
-    a.in_step = 1; a.Hs = H; a.Ws = W; a.N = N; a.H = H; a.W = W; a.nz = 1; a.out_step = 1; a.Hd = H; a.Wd = W;
-    a.act = act; a.leaky_slope = slope; a.bias = bias; a.wpack = wpack;
+    // (the kernels read the bias as fp32 from device memory: the caller's tensor is used as is -- cout_real values, padded reads are masked by cout_real)
     if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone, C = 16, 32 or 64
-        const int C = cout_real, CO = C < 32 ? 32 : C;
+        const int C = cout_real;
         if (ks != 3 || !layer_width_ok(C) || !y_pm || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
-        a.CD = C; a.cout_real = C; a.dst[0] = y_pm; a.dst_nstride = pm_image_elems(H, W, C);
-        if (x_pm) {
-            if (cin_pm != C || cin_real != C + 3) return VSR_ERR_UNSUPPORTED;
-            CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, C, C, C, C + 3, 3, 1, 0, 0, st));
-            CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)9 * CO * C * es, 9, CO, 16, C, 3, C + 3, 0, 1, 0, 0, st));
-            a.src[0] = x_pm; a.src_nstride[0] = pm_image_elems(H, W, C);
-            a.src[1] = lr_planar; a.src_nstride[1] = (long long)3 * H * W;
-            return vsr_launch_conv(dtype, 3, 2, C, 16, 1, CO, EPI_NHWC, a, st);
-        }
-        if (cin_real != 3) return VSR_ERR_UNSUPPORTED;
-        CK(vsr_launch_pack_weights(dtype, w, wp, 9, CO, 16, C, 3, 3, 0, 1, 0, 0, st));
-        a.src[0] = lr_planar; a.src_nstride[0] = (long long)3 * H * W;
-        return vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st);
+        const bool cat = x_pm != nullptr;
+        if (cat ? (cin_pm != C || cin_real != C + 3) : cin_real != 3) return VSR_ERR_UNSUPPORTED;
+        const Ctx c(nullptr, st, dtype, C);
+        CK(c.pack_stem(w, wp, cat));
+        return c.stem(cat, x_pm, lr_planar, (long long)3 * H * W, wp, b, y_pm, act, slope, N, H, W);
     }
-    a.src[0] = x_pm; a.src_nstride[0] = pm_image_elems(H, W, cin_pm);
     if (ks == 3 || ks == 1) {
-        const int C = cin_pm, CO = C < 32 ? 32 : C;
+        const int C = cin_pm;
         if (!layer_width_ok(C) || cin_real != C) return VSR_ERR_UNSUPPORTED;
+        const Ctx c(nullptr, st, dtype, C);
         if (pixel_shuffle) {
             if (ks != 3 || cout_real != 4 * C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-            for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(dtype, w, wp + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, 0, st));
-            // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c + 2i + j]: sub-conv z uses rows 4c+z and bias entries 4c+z
-            float* b4 = reinterpret_cast<float*>(wp + (size_t)4 * 9 * CO * C * es);
-            if (b) for (int z = 0; z < 4; ++z) CK(vsr_launch_pack_weights(VSR_F32, b, b4 + z * C, 1, C, 1, C, 1, 1, 0, 4, z, 0, st));
-            a.bias = b ? b4 : nullptr; a.bias_zstride = C; a.nz = 4; a.w_zstride = 9 * CO * C;
-            a.out_step = 2; a.Hd = 2 * H; a.Wd = 2 * W; a.CD = C; a.cout_real = C; a.dst_nstride = pm_image_elems(2 * H, 2 * W, C);
-            for (int z = 0; z < 4; ++z) { a.dst[z] = y_pm; a.out_oy[z] = z >> 1; a.out_ox[z] = z & 1; }
-            return vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st);
+            CK(c.pack_ps(w, wp, 0));
+            float* b4 = reinterpret_cast<float*>(wp + (size_t)4 * 9 * c.CO * C * c.es);
+            if (b) CK(c.pack_ps_bias(b, b4));
+            return c.conv_ps(x_pm, wp, b ? b4 : nullptr, y_pm, N, H, W, act, slope);
         }
         if (cout_real != C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-        CK(vsr_launch_pack_weights(dtype, w, wp, ks * ks, CO, C, C, C, C, 0, 1, 0, 0, st));
-        a.CD = C; a.cout_real = C; a.dst[0] = y_pm; a.dst_nstride = pm_image_elems(H, W, C);
-        return vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st);
+        CK(c.pack_cc(ks, w, wp, 0));
+        return c.conv(ks, x_pm, wp, b, y_pm, act, nullptr, nullptr, 0, N, H, W, nullptr, nullptr, false, slope);
     }
     if (ks != 7 || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
     for (int j = 0; j < NSPY; ++j) {
         if (cin_pm != SPY_CIP[j] || cout_real != SPY_CO[j] || cin_real != SPY_CI[j]) continue;
-        CK(vsr_launch_pack_weights(dtype, w, wp, 49, SPY_COP[j], SPY_CIP[j], SPY_CO[j], SPY_CI[j], SPY_CI[j], 0, 1, 0, 0, st));
-        a.cout_real = SPY_CO[j];
-        if (j < NSPY - 1) {
-            if (!y_pm || cd != SPY_CD[j]) return VSR_ERR_BADARG;
-            a.dst[0] = y_pm; a.CD = SPY_CD[j]; a.dst_nstride = pm_image_elems(H, W, SPY_CD[j]);
-            return vsr_launch_conv(dtype, 7, 1, SPY_CIP[j], SPY_CIP[j], 0, SPY_COP[j], EPI_NHWC, a, st);
-        }
-        if (!y_planar) return VSR_ERR_BADARG;
-        a.dst[0] = y_planar; a.dst_nstride = (long long)2 * H * W;
-        return vsr_launch_conv(dtype, 7, 1, 16, 16, 0, 32, EPI_PLANAR, a, st);
+        const Ctx c(nullptr, st, dtype);
+        CK(c.pack_spy(j, w, wp, 0));
+        if (j < NSPY - 1 ? (!y_pm || cd != SPY_CD[j]) : !y_planar) return VSR_ERR_BADARG;
+        return c.spy_conv(j, x_pm, wp, b, j < NSPY - 1 ? y_pm : (void*)y_planar, act, slope, nullptr, N, H, W);
     }
     return VSR_ERR_UNSUPPORTED;
 }
 
-size_t vsr_conv3x3_c64_wgrad_slab_floats(void) {
-    int cp, xp, stride;
-    vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-    return (size_t)VSR_WGRAD_NWG * stride;
-}
+size_t vsr_conv3x3_c64_wgrad_slab_floats(void) { return wgrad_slab_floats(); }
 
 int vsr_conv3x3_c64_wgrad(int dtype, const void* x_pm, const void* dy_pm, float* gw, float* gb, float* slab, int N, int H, int W,
                           void* stream) {
     if (bad_dtype(dtype) || !x_pm || !dy_pm || !gw || !slab || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    hipStream_t st = (hipStream_t)stream;
+    const Ctx c(nullptr, (hipStream_t)stream, dtype, 64, slab);
     WgradArgs a = wg_base(N, H, W);
     a.x[0] = x_pm; a.dy[0] = dy_pm;
-    int cp, xp, stride;
-    vsr_wgrad_slab_dims(3, 64, 64, &cp, &xp, &stride);
-    a.slab = slab; a.slab_stride = stride;
-    const int tiles = N * cdiv(H, 8) * cdiv(W, 32);
-    const int nwg = tiles < VSR_WGRAD_NWG ? tiles : VSR_WGRAD_NWG;
-    int nslabs = 0;
-    CK(vsr_launch_wgrad(dtype, 3, 64, 0, 64, 0, a, nwg, &nslabs, st));
-    return vsr_launch_wgrad_reduce(slab, nslabs, 3, 64, 64, C, C, gw, C, 0, 1, 0, gb, 0, st);
+    return c.wgrad(a, {3, 64, false, 64, false}, {C, C, gw, C, 0, 1, 0, gb, 0}, false);      // an odd tile count stays odd: wgrad_run()
 }
 
 size_t vsr_charbonnier_scratch_floats(void) { return (size_t)vsr_charbonnier_scratch_floats_impl(); }

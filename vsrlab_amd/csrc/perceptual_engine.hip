@@ -17,8 +17,7 @@
 // the hr tap), and the data-gradient chain runs from conv5_4 down to the planar fp32 d sr.  Each backward layer writes into the
 // buffer of an activation that is no longer needed, so the backward needs no scratch of its own.
 #include <vector>
-#include "kernels.h"
-#include "../../include/vsrlab_hip.h"
+#include "host.h"
 
 namespace {
 
@@ -31,8 +30,6 @@ constexpr int L_CO[NCONV] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512
 constexpr int L_CI[NCONV] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512, 512, 512};
 constexpr int L_LV[NCONV] = {0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4};
 constexpr int TAP_CONV[NTAP] = {1, 3, 7, 11, 15};      // conv (by position) whose output is tap '2', '7', '16', '25', '34'
-
-#define CK(expr) do { int _s = (expr); if (_s != VSR_OK) return _s; } while (0)
 
 // ============================================== kernels =============================================================
 template <typename T> __device__ __forceinline__ void pld8(const T* p, float* f);
@@ -194,11 +191,6 @@ __global__ void tap_sum_kernel(const double* __restrict__ partial, double* __res
 }
 
 // =============================================== plan ===============================================================
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
-};
-
 struct PPlan {
     int n, h, w, dtype, need_grad; size_t es;
     int Hl[5], Wl[5];
@@ -214,7 +206,7 @@ struct PPlan {
         n = d.n; h = d.h; w = d.w; dtype = d.dtype; need_grad = d.need_grad;
         if (dtype != VSR_F32 && dtype != VSR_BF16) return VSR_ERR_BADARG;
         if (n < 1 || h < 16 || w < 16 || n > 65535 || h > 65535 || w > 65535) return VSR_ERR_UNSUPPORTED;
-        es = dtype == VSR_BF16 ? 2 : 4;
+        es = esize(dtype);
         Hl[0] = h; Wl[0] = w;
         for (int l = 1; l < 5; ++l) { Hl[l] = Hl[l - 1] / 2; Wl[l] = Wl[l - 1] / 2; }
         Bump b;

@@ -355,6 +355,39 @@ int vsr_window_attention_bwd(const VsrAttnDesc* d, const void* qkv, const float*
 int vsr_rpb_gather(const float* table, const long long* index, int idx_stride, float* dense, int heads, int N, void* stream);
 int vsr_rpb_scatter(const float* ddense, const long long* index, int idx_stride, float* dtable, int heads, int N, void* stream);
 
+/* ---- Deformable convolution and VRT's flow-guided alignment (csrc/deform_conv.hip) ----------------
+ * torchvision.ops.deform_conv2d(x, offset, weight, bias, 1, 1, 1, mask) for a 3x3 kernel, stride 1, padding 1, dilation 1,
+ * groups 1 (core/modules/conv.py:33-80, vsr/models/VRT/modules/deform_conv.py:8-145).  All tensors fp32 planar:
+ *   x (N,Cin,H,W), weight (Cout,Cin,3,3), bias (Cout) or NULL, y (N,Cout,H,W);
+ *   offset (N, 2*dg*9, H, W): channel 2*(g*9+k) = dy, +1 = dx of group g, tap k = 3i+j; mask (N, dg*9, H, W).
+ * Sample position py = y-1+i+dy, px = x-1+j+dx; bilinear, a corner counts only inside the image; the sample times the mask is
+ * shared by the Cin/dg channels of the group.  modulated = 0: `mask` is NULL (= 1).
+ * flow_guided = 1 (modulated = 1): `offset` is the RAW output of conv_offset (N, 27*dg, H, W), `flow` (N,2,H,W), channel 0 = x;
+ *   offset[c] = max_residue * tanh(raw[c]) + (flow_y for even c, flow_x for odd c), c < 18*dg; mask = sigmoid(raw[18*dg + m]);
+ *   `mask` is NULL.  The backward then returns d raw in `doffset` and d flow in `dflow`.
+ * dtype: element type of the staged x, the gathered columns and the weights (fp32 accumulation); offsets, masks, flow and the
+ * bilinear weights are fp32 in either build.  Cin, Cout <= 192, deform_groups divides Cin and the groups, each padded to 8 or
+ * a multiple of 16 channels, fit 192: anything else is VSR_STATUS_UNSUPPORTED (workspace_bytes: 0).
+ * Workspace: need_backward = 0 is what _fwd needs, 1 what _bwd needs; the calls are independent (the backward re-stages x
+ * and recomputes the columns, nothing is kept between them).  NULL gradient pointers mean "not wanted".
+ * dweight, dbias, doffset, dmask, dflow are bit-identical across runs; dx is accumulated with fp32 atomic adds (reproducible
+ * to rounding only).                                                                                                   */
+typedef struct VsrDeformDesc {
+    int N, Cin, Cout, H, W;
+    int deform_groups;
+    int modulated, flow_guided;
+    float max_residue;
+    int dtype;
+} VsrDeformDesc;
+size_t vsr_deform_conv_workspace_bytes(const VsrDeformDesc* d, int need_backward);      /* 0: unsupported descriptor */
+int vsr_deform_conv_fwd(const VsrDeformDesc* d, const float* x, const float* offset, const float* mask, const float* flow,
+                        const float* weight, const float* bias, float* y, void* workspace, size_t workspace_bytes, void* stream);
+int vsr_deform_conv_bwd(const VsrDeformDesc* d, const float* x, const float* offset, const float* mask, const float* flow,
+                        const float* weight, const float* dy, float* dx, float* doffset, float* dmask, float* dflow,
+                        float* dweight, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+/* the flow-guided epilogue on its own (flow_guided = 1): offset and mask as the fused calls form them, bit for bit */
+int vsr_deform_offset_mask(const VsrDeformDesc* d, const float* out, const float* flow, float* offset, float* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,12 @@ class AttnDesc(ctypes.Structure):
                [("scale", c_float), ("dtype", c_int), ("mask_packed", c_int), ("mask_value", c_float)]
 
 
+class DeformDesc(ctypes.Structure):
+    """struct VsrDeformDesc (include/vsrlab_hip.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "Cin", "Cout", "H", "W", "deform_groups", "modulated", "flow_guided")] + \
+               [("max_residue", c_float), ("dtype", c_int)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -97,6 +103,10 @@ _SIGNATURES = {
     "vsr_mask_pack": (c_int, [_P, _P, c_int, c_int, _P]),
     "vsr_rpb_gather": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P]),
     "vsr_rpb_scatter": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P]),
+    "vsr_deform_conv_workspace_bytes": (c_size_t, [ctypes.POINTER(DeformDesc), c_int]),
+    "vsr_deform_conv_fwd": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_deform_conv_bwd": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_deform_offset_mask": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

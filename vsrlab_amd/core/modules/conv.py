@@ -4,9 +4,13 @@ arguments, same parameter names (``conv.0.weight``, ``res_block.{i}.conv1.weight
 checkpoints load strictly.  Inside ``BasicVSR`` / ``Spynet`` / ``UNetDiscriminator`` the whole network runs in one engine
 call and these modules are its parameter containers; called on their own they dispatch to the per-layer kernels
 (all differentiable: ``ResidualConv`` through its fused forward/backward function, ``ConvReLU`` and the ``ResidualBlock`` stem through
-``vsr_conv_layer_fwd`` / ``vsr_conv_layer_bwd``)."""
+``vsr_conv_layer_fwd`` / ``vsr_conv_layer_bwd``).  ``DeformConv`` / ``DeformBlock`` (:33-80) run their deformable convolution
+in ``vsr_deform_conv_fwd`` / ``_bwd``."""
+import math
+
 import torch
 import torch.nn as nn
+from torch.nn.modules.utils import _pair
 
 from ... import functional as VF
 
@@ -86,3 +90,55 @@ class ResidualBlock(nn.Module):
     def forward(self, x):
         blocks = [(b.conv1.weight, b.conv1.bias, b.conv2.weight, b.conv2.bias) for b in self.res_block]
         return VF.residual_block_forward(x, self.conv[0].weight, self.conv[0].bias, blocks)
+
+
+class DeformConv(nn.Module):
+    """Deformable convolution pack (conv.py:33-65).  The reference inherits ``torchvision.ops.DeformConv2d``; this class carries the
+    same attributes, parameter names (``weight``, ``bias``, ``conv_offset.*``) and initialisation (kaiming-uniform(a=sqrt 5) weight,
+    fan-in bias, zero offset convolution) without torchvision.  No modulation mask."""
+
+    def __init__(self, deformable_groups, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding, self.dilation = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
+        self.groups = groups
+        self.deformable_groups = deformable_groups
+        if (self.kernel_size, self.stride, self.padding, self.dilation, groups) != ((3, 3), (1, 1), (1, 1), (1, 1), 1):
+            raise NotImplementedError("HIP DeformConv: kernel 3x3, stride 1, padding 1, dilation 1, groups 1 (what DeformBlock instantiates); "
+                                      f"got kernel {kernel_size}, stride {stride}, padding {padding}, dilation {dilation}, groups {groups}")
+        if in_channels % deformable_groups:
+            raise ValueError(f"deformable_groups ({deformable_groups}) must divide in_channels ({in_channels})")
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, *self.kernel_size))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            bound = 1 / math.sqrt(self.weight.shape[1] * self.kernel_size[0] * self.kernel_size[1])
+            nn.init.uniform_(self.bias, -bound, bound)
+        self.conv_offset = nn.Conv2d(in_channels, deformable_groups * 2 * self.kernel_size[0] * self.kernel_size[1], self.kernel_size,
+                                     self.stride, self.padding, self.dilation, self.groups)
+        self.init_offset()
+
+    def init_offset(self):
+        self.conv_offset.weight.data.zero_()
+        self.conv_offset.bias.data.zero_()
+
+    def forward(self, x):
+        offset = self.conv_offset(x).float()
+        return VF.deform_conv2d(x, offset, self.weight, self.bias, stride=self.stride, padding=self.padding, dilation=self.dilation)
+
+
+class DeformBlock(nn.Module):
+    """conv3x3, ``blocks`` x DeformConv(deformable_groups=1), conv3x3  (conv.py:67-80)."""
+
+    def __init__(self, in_channels, mid_channels, blocks):
+        super().__init__()
+        self.conv_in = nn.Conv2d(in_channels, mid_channels, 3, 1, 1)
+        self.dcblock = nn.Sequential(*[DeformConv(deformable_groups=1, in_channels=mid_channels, out_channels=mid_channels, kernel_size=3,
+                                                  padding=1) for _ in range(blocks)])
+        self.conv_out = nn.Conv2d(mid_channels, in_channels, 3, 1, 1)
+
+    def forward(self, x):
+        return self.conv_out(self.dcblock(self.conv_in(x)))

@@ -36,24 +36,18 @@
 // instruction may otherwise overwrite the data registers before the store has read them) and the first vector-memory asm
 // behind the scalar adds of its base starts with `s_nop 4` (cdna_hip_programming.md 5.7).
 //
-// The tile loop itself (K loop, fragment schedule, epilogues) is conv3x3_persist.hip's; see there for the LDS images.
-#include "common.h"
+// The tile core (LDS images, weight staging, the producers' DMA, K loop, fragment schedule, packed-word epilogue arms) is shared with
+// conv3x3_persist.hip: conv3x3_c64_tile.h, described there.  Here: hand-out, flags, publish, the sc1 memory operations.
+#include "conv3x3_c64_tile.h"
 #include "kernels.h"
 #include <atomic>
 #include <type_traits>
 
 namespace {
 
-constexpr int PTW = 32, PTH = 8, PNT = 512;
-constexpr int PTWH = PTW + 2, PTHH = PTH + 2, PNPIX = PTHH * PTWH;
-constexpr int W_BYTES = 9 * 64 * 64 * 2;
-constexpr int IN_BYTES = PNPIX * 128;
-constexpr int BIAS_OFF = W_BYTES + 2 * IN_BYTES;
 constexpr int CTL_OFF = BIAS_OFF + 256;                                   // 3 item slots of 8 ints
 constexpr int P_LDS = CTL_OFF + 128;                                      // 161,152 <= 163,840
-constexpr int IN_CHUNKS = PNPIX * 8;
-constexpr int NPIECE_T = (IN_CHUNKS + 63) / 64;
-constexpr int NPIECE_W = (NPIECE_T + 3) / 4;                              // 11; the leader wave (w4 = 0) always issues exactly 11
+constexpr int DMA_SC1 = 16;                                               // the tile DMA bypasses the CU's L1
 
 // The energy of the LDS reads, DMA and stores was priced with ablated builds of this file: DESIGN 4.1c.
 #ifdef VSR_CLOCK
@@ -72,21 +66,6 @@ __device__ unsigned g_chain_timeouts;           // waits given up since the modu
 typedef __attribute__((address_space(1))) unsigned gu32;
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    bf16x2_t p = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ unsigned pk_max_i16(unsigned a, unsigned b) { unsigned r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-#define GLDS16_SC1(src, dst)                                                                          \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, 16)
-#define GP(T, x) ((__attribute__((address_space(1))) T*)(x))
 
 // The 3 x 3 tiles around (ty, tx) of one layer's image have been published by all four of their MFMA waves: flg points at the
 // image's first tile, one 16-byte record of four flag words per tile; lanes 0..8 look at one tile each (two 8-byte sc1 loads).
@@ -161,7 +140,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
     const int role = __builtin_amdgcn_readfirstlane(wave >> 2);            // 0: MFMA + epilogue, 1: LDS-DMA producer
     const int w4 = __builtin_amdgcn_readfirstlane(wave & 3);
     const int l15 = lane & 15, q = lane >> 4;
-    const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
+    const int pxl = PM_LANE_PIXEL(l15);
     char* lds_w = smem;
     char* lds_t = smem + W_BYTES;
     int* const ctl = reinterpret_cast<int*>(smem + CTL_OFF);              // slot s: ctl + 8 s = {item, layer, n, ty, tx, ready, -, -}
@@ -201,33 +180,12 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
     __syncthreads();
     if (ctl[0] < 0) return;                                                // more workgroups than items (uniform)
 
-#define W_LOAD(wv, wg)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < WCH; ++i) {                                                                    \
-        const int idx = (tid & 255) + i * 256;        /* 256 threads stage a weight set: the MFMA waves or the producers */ \
-        const int tap = idx >> 9, r = (idx >> 3) & 63, c = idx & 7;                                                      \
-        wv[i] = (wg)[(tap * 64 + pm_acc_chan(r >> 4, r & 15)) * 8 + c];                                                  \
-    }
-#define W_STORE(wv)                                                                                                      \
-    _Pragma("unroll") for (int i = 0; i < WCH; ++i) {                                                                    \
-        const int idx = (tid & 255) + i * 256;                                                                           \
-        const int tap = idx >> 9, r = (idx >> 3) & 63, c = idx & 7;                                                      \
-        *reinterpret_cast<u32x4_t*>(lds_w + tap * 8192 + (r * 8 + (c ^ ((r >> 1) & 7))) * 16) = wv[i];                 \
-    }
-    constexpr int WCH = 9 * 64 * 8 / 256;
-
     if (role == 1) {
         // =================== producer waves ===================
         const bool leader = w4 == 0;
         const auto* zsrc = GP(const char, g_chain_zero_chunk);
         int rel[NPIECE_W];
-#pragma unroll
-        for (int i = 0; i < NPIECE_W; ++i) {
-            const int idx = (w4 + 4 * i) * 64 + lane;
-            const int ty = idx / (8 * PTWH), rem = idx - ty * (8 * PTWH);
-            const int c = rem / PTWH, tx = rem - c * PTWH;
-            const int dx = tx - 1;
-            rel[i] = ((((ty - 1) * WS + (dx >> 5)) * 8 + c) * 256 + (dx & 31) * 8) * 2;
-        }
+        C64_DMA_REL(rel, w4, lane, 1, 0, 0, WS)
         u32x4_t wvp[WCH];                                          // the next layer's weights on their way to LDS
         float bvp = 0.f;
         const int pt = tid - 256;
@@ -238,24 +196,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
             const int ty0 = tyi * PTH, tx0 = txi * PTW;
             const auto* org = GP(const char, p_src) + ((long long)n * img + pm_off(ty0, tx0, 0, W, 64)) * 2;
             char* dstb = lds_t + buf * IN_BYTES;
-            if (ty0 >= 1 && ty0 + PTH < H && tx0 >= 1 && tx0 + PTW < W) {
-#pragma unroll
-                for (int i = 0; i < NPIECE_W; ++i) {
-                    const int piece = w4 + 4 * i;
-                    if (piece < NPIECE_T && piece * 64 + lane < IN_CHUNKS) GLDS16_SC1(org + rel[i], dstb + piece * 1024);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NPIECE_W; ++i) {
-                    const int piece = w4 + 4 * i;
-                    const int idx = piece * 64 + lane;
-                    const int ty = idx / (8 * PTWH), rem = idx - ty * (8 * PTWH);
-                    const int tx = rem % PTWH;
-                    const int vy = ty0 + ty - 1, vx = tx0 + tx - 1;
-                    const auto* s = (vy >= 0 && vy < H && vx >= 0 && vx < W) ? org + rel[i] : zsrc;
-                    if (piece < NPIECE_T && idx < IN_CHUNKS) GLDS16_SC1(s, dstb + piece * 1024);
-                }
-            }
+            C64_DMA_TILE(DMA_SC1, rel, org, zsrc, dstb, w4, lane, ty0, tx0, H, W)
         };
         // item 0: nothing was polled for it yet
         {
@@ -279,7 +220,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 // the weight image is free (every MFMA wave is past the K loop of the previous tile: the barrier that ended it).
                 // Before, the MFMA waves loaded, waited and wrote here, with the L2 round trip exposed once per layer and workgroup.
                 cur_layer = layer_k;
-                W_STORE(wvp)
+                C64_W_STORE(wvp, lds_w, tid & 255)
                 if (pt < 64) reinterpret_cast<float*>(smem + BIAS_OFF)[pt] = bvp;
                 __syncthreads();
             }
@@ -292,7 +233,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 const int l1w = __builtin_amdgcn_readfirstlane(s1[1]);
                 if (l1w != cur_layer) {
                     const auto* wgx = GP(const u32x4_t, base + (unsigned long long)ka.layer[l1w].w * 256ull);
-                    W_LOAD(wvp, wgx)
+                    C64_W_LOAD(wvp, wgx, tid & 255)
                     const unsigned bo = ka.layer[l1w].bias;
                     bvp = 0.f;
                     if (pt < 64 && bo != 0xffffffffu) bvp = GP(const float, base + (unsigned long long)bo * 256ull)[pm_acc_chan(pt >> 4, pt & 15)];
@@ -340,22 +281,16 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
         u32x4_t wv[WCH];                                           // the FIRST layer's weights (prologue only: the producers are busy with the first tile)
         {
             const auto* wg = GP(const u32x4_t, base + (unsigned long long)ka.layer[ctl[1]].w * 256ull);
-            W_LOAD(wv, wg)
+            C64_W_LOAD(wv, wg, tid & 255)
         }
-        unsigned a_lo[2], a_hi[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            a_lo[kk] = (unsigned)((l15 * 8 + ((4 * kk + q) ^ ((l15 >> 1) & 7))) * 16);
-            a_hi[kk] = a_lo[kk] + 6 * 8192;
-        }
-        const int b_lane = w4 * 2 * (PTWH * 128) + q * (PTWH * 16) + pxl * 16;
+        C64_MFMA_LANE(w4, l15, q, pxl)
         unsigned loff[4];
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
             const int dx = (nb & 1) * 16 + pxl;
             loff[nb] = (((((w4 * 2 + (nb >> 1))) * WS + (dx >> 5)) * 8 + q) * 256 + (dx & 31) * 8) * 2;     // BYTES from the tile's origin
         }
-        W_STORE(wv)
+        C64_W_STORE(wv, lds_w, tid & 255)
         if (tid < 64) {
             const unsigned bo = ka.layer[ctl[1]].bias;
             reinterpret_cast<float*>(smem + BIAS_OFF)[tid] = bo != 0xffffffffu ? GP(const float, base + (unsigned long long)bo * 256ull)[pm_acc_chan(tid >> 4, tid & 15)] : 0.f;
@@ -364,12 +299,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
         __syncthreads();
         f32x4_t bvec[4];
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) bvec[mb] = *reinterpret_cast<const f32x4_t*>(smem + BIAS_OFF + (mb * 16 + 4 * q) * 4);
-        bf16x8_t idA[2];
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) idA[hb][j] = (bf16_t)((q == (l15 >> 2) && j == 4 * hb + (l15 & 3)) ? 1.f : 0.f);
+        for (int mb = 0; mb < 4; ++mb) bvec[mb] = c64_bias_rows(smem, q, mb);
+        C64_RES_IDENTITY(idA, l15, q)
 
         // the layer whose operands are loaded
         int cur_layer = __builtin_amdgcn_readfirstlane(ctl[1]);
@@ -400,7 +331,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 layer_ptrs(layer);
                 __syncthreads();
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb) bvec[mb] = *reinterpret_cast<const f32x4_t*>(smem + BIAS_OFF + (mb * 16 + 4 * q) * 4);
+                for (int mb = 0; mb < 4; ++mb) bvec[mb] = c64_bias_rows(smem, q, mb);
             }
             const int tile = item - layer * tiles;
             const int ty0 = tyi * PTH, tx0 = txi * PTW;
@@ -416,7 +347,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                 constexpr bool HAS_RES = V == CHAIN_SKIP, BITS = V == CHAIN_MASK;
                 u32x4_t rr[2][4];
                 u32x2_t sbits = {0u, 0u};
-                if (BITS) sbits = GP(const u32x2_t, p_sbits)[(long long)tile * 256 + w4 * 64 + lane];
+                if (BITS) sbits = GP(const u32x2_t, p_sbits)[c64_sign_word(tile, w4, lane)];
                 if (HAS_RES) {
                     // the residual = the output of layer - 2 of this chain (or the chain's input): write-through stored there, sc1 here
                     const unsigned long long rbase = p_res + (unsigned long long)tbase * 2ull;
@@ -439,51 +370,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                     }
                 }
                 f32x4_t acc[4][4];
-                bf16x8_t fa[2][4], fb[2][4];
-                const unsigned bb = (unsigned)(W_BYTES + cur * IN_BYTES + b_lane);
-#define DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
-#define CV_LOADA(tap_, kk_, slot, mb) DSR(fa[slot][mb], tap_ < 6 ? a_lo[kk_] : a_hi[kk_], (tap_ < 6 ? tap_ : tap_ - 6) * 8192 + (mb) * 2048);
-#define CV_LOADB(ky_, kx_, kk_, slot, nb) DSR(fb[slot][nb], bb, (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
-#define CV_LOAD(s, slot)                                                                                               \
-                {                                                                                                      \
-                    constexpr int tap_ = (s) / 2, kk_ = (s) % 2, ky_ = tap_ / 3, kx_ = tap_ % 3;                       \
-                    CV_LOADA(tap_, kk_, slot, 0) CV_LOADA(tap_, kk_, slot, 1) CV_LOADA(tap_, kk_, slot, 2) CV_LOADA(tap_, kk_, slot, 3) \
-                    CV_LOADB(ky_, kx_, kk_, slot, 0) CV_LOADB(ky_, kx_, kk_, slot, 1) CV_LOADB(ky_, kx_, kk_, slot, 2) CV_LOADB(ky_, kx_, kk_, slot, 3) \
-                }
-#define CV_MFMA(s, mb, nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[(s) % 2][mb], fb[(s) % 2][nb], (s) == 0 ? bvec[mb] : acc[mb][nb], 0, 0, 0);
-#define CV_ML_A(s, mb, nb, lmb)                                                                                        \
-                CV_MFMA(s, mb, nb)                                                                                     \
-                __builtin_amdgcn_sched_barrier(0);                                                                     \
-                if ((s) + 1 < 18) { constexpr int t1_ = ((s) + 1) / 2, k1_ = ((s) + 1) % 2; CV_LOADA(t1_, k1_, ((s) + 1) % 2, lmb) } \
-                __builtin_amdgcn_sched_barrier(0);
-#define CV_ML_B(s, mb, nb, lnb)                                                                                        \
-                CV_MFMA(s, mb, nb)                                                                                     \
-                __builtin_amdgcn_sched_barrier(0);                                                                     \
-                if ((s) + 1 < 18) { constexpr int t1_ = ((s) + 1) / 2, k1_ = ((s) + 1) % 2; CV_LOADB(t1_ / 3, t1_ % 3, k1_, ((s) + 1) % 2, lnb) } \
-                __builtin_amdgcn_sched_barrier(0);
-#define CV_STEP(s)                                                                                                     \
-                {                                                                                                      \
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                    CV_ML_A(s, 0, 0, 0) CV_ML_A(s, 0, 1, 1) CV_ML_A(s, 0, 2, 2) CV_ML_A(s, 0, 3, 3)                    \
-                    CV_ML_B(s, 1, 0, 0) CV_ML_B(s, 1, 1, 1) CV_ML_B(s, 1, 2, 2) CV_ML_B(s, 1, 3, 3)                    \
-                    CV_MFMA(s, 2, 0) CV_MFMA(s, 2, 1) CV_MFMA(s, 2, 2) CV_MFMA(s, 2, 3)                                \
-                    CV_MFMA(s, 3, 0) CV_MFMA(s, 3, 1) CV_MFMA(s, 3, 2) CV_MFMA(s, 3, 3)                                \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                CV_LOAD(0, 0)
-                CV_STEP(0) CV_STEP(1) CV_STEP(2) CV_STEP(3) CV_STEP(4) CV_STEP(5) CV_STEP(6) CV_STEP(7) CV_STEP(8)
-                CV_STEP(9) CV_STEP(10) CV_STEP(11) CV_STEP(12) CV_STEP(13) CV_STEP(14) CV_STEP(15) CV_STEP(16) CV_STEP(17)
-#undef CV_ML_A
-#undef CV_ML_B
-#undef CV_STEP
-#undef CV_MFMA
-#undef CV_LOAD
-#undef CV_LOADB
-#undef CV_LOADA
-#undef DSR
+                C64_K_LOOP(acc, bvec, cur)
                 nx_item = sn[0]; nx_layer = sn[1]; nx_n = sn[2]; nx_ty = sn[3]; nx_tx = sn[4]; nx_ok = sn[5];
                 // ---- epilogue ----
                 // vmcnt(0): this tile's operands are here, and the PREVIOUS tile's stores (issued a K loop ago) are acknowledged:
@@ -496,15 +383,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                     if (lane == 0 && CHAIN_PUBLISH) __hip_atomic_store(pend_cnt, 1u, RLX_AGENT);
                     pending = false;
                 }
-                if constexpr (HAS_RES) {
-#pragma unroll
-                    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 4; ++mb)
-                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(idA[mb & 1], __builtin_bit_cast(bf16x8_t, rr[mb >> 1][nb]), acc[mb][nb], 0, 0, 0);
-                }
+                if constexpr (HAS_RES) { C64_ADD_RESIDUAL(acc, idA, rr) }
                 unsigned sout[2] = {0u, 0u};
-                const unsigned k11 = 0x00010001u;
                 const unsigned long long dbase = p_dst + (unsigned long long)tbase * 2ull;
                 auto epilogue = [&](auto FULL) {
                     const unsigned long long db = dbase;          // (asm operands do not capture by themselves in a generic lambda)
@@ -519,20 +399,9 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                                 for (int j = 0; j < 4; ++j) { v[j] = acc[2 * kq][nb][j]; v[4 + j] = acc[2 * kq + 1][nb][j]; }
                                 const unsigned wbits = kq ? sbits.y : sbits.x;
                                 unsigned ow[4];
-                                if (V == CHAIN_RELU) {
-#pragma unroll
-                                    for (int jj = 0; jj < 4; ++jj) {
-                                        ow[jj] = pk_max_i16(pk_bf16(v[2 * jj], v[2 * jj + 1]), 0u);
-                                        sout[kq] |= pk_min_u16(ow[jj], k11) << (4 * nb + jj);
-                                    }
-                                } else if (V == CHAIN_MASK) {
-#pragma unroll
-                                    for (int jj = 0; jj < 4; ++jj)
-                                        ow[jj] = pk_mul_lo_u16(pk_bf16(v[2 * jj], v[2 * jj + 1]), (wbits >> (4 * nb + jj)) & k11);
-                                } else {
-#pragma unroll
-                                    for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_bf16(v[2 * jj], v[2 * jj + 1]);
-                                }
+                                if (V == CHAIN_RELU) { C64_ARM_RELU(ow, v, nb, sout[kq]) }
+                                else if (V == CHAIN_MASK) { C64_ARM_MASKED(ow, v, nb, wbits) }
+                                else { C64_ARM_PLAIN(ow, v) }
                                 const u32x4_t o = {ow[0], ow[1], ow[2], ow[3]};
                                 // write-through: the next layer's tiles may be loaded on another XCD
                                 // (asm: `s_nop 1` behind a 16-byte store, or hipcc's next instruction may overwrite the data registers before
@@ -546,7 +415,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_chain_kernel(const ChainAr
                     }
                 };
                 if (full) epilogue(std::true_type{}); else epilogue(std::false_type{});
-                if (V == CHAIN_RELU && p_sout) GP(u32x2_t, p_sout)[(long long)tile * 256 + w4 * 64 + lane] = u32x2_t{sout[0], sout[1]};
+                if (V == CHAIN_RELU && p_sout) GP(u32x2_t, p_sout)[c64_sign_word(tile, w4, lane)] = u32x2_t{sout[0], sout[1]};
             };
             if (variant == CHAIN_SKIP) body(std::integral_constant<int, CHAIN_SKIP>{});
             else body(std::integral_constant<int, EVEN>{});

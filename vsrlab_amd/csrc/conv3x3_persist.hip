@@ -5,46 +5,19 @@
 // At 540p one launch moves 133-200 MB for 38 GFLOP: 21-32 us at the 6.3 TB/s a CU-side stream reaches,
 // 15 us on the matrix cores -- the kernel is HBM-bound, and a CU needs ~75 KB in flight to cover ~3 us of
 // loaded HBM latency.  Design for one MI355X CU (160 KiB LDS, 4 SIMDs):
-//   * ONE 512-thread workgroup per CU, grid = #CUs, persistent over 8x32-pixel tiles (one 32-pixel segment
-//     of the blocked layout wide, see common.h): 4 MFMA waves + 4 LDS-DMA producer waves, one of each per
-//     SIMD.  The packed weights [9 taps][64 cout][64 cin] bf16 (72 KiB) are loaded into LDS once and stay.
-//   * the haloed 10x34-pixel input tile is DOUBLE-BUFFERED in LDS (2 x 42.5 KiB) and filled by the producer
-//     waves' LDS-DMA (global_load_lds_dwordx4) one whole tile ahead; the residual / mask operands of the
-//     epilogue are requested into registers before the K loop.  Nothing the tile needs is waited for at first use.
-//   * K loop: 288 v_mfma_f32_16x16x32_bf16 per MFMA wave and tile, no barrier inside; A (weights) and B (pixels)
-//     fragments are ds_read_b128 at register base + immediate, issued by hand one k-step ahead of their
-//     MFMAs (inline asm + counted s_waitcnt: hipcc sinks builtin LDS reads back in front of their
-//     consumers).  The weight image is
-//     [cout row][8 chunks of 16 B], XOR-swizzled on the chunk; the pixel image mirrors the blocked global
-//     layout, [tile row][chunk][34 pixels][16 B]: 16 consecutive lanes read 16 consecutive 16-byte slots
-//     (conflict-free without a swizzle), a ky shift is an immediate, and a DMA piece reads runs of up to 512
-//     contiguous bytes (a [pixel][chunk] image made every lane of a piece hit a different line:
-//     +40 % DMA issue time measured).
-//   * epilogue: the accumulator layout (lane = pixel of the segment, registers = 4 consecutive rows of a 16-row block) IS
-//     the blocked global layout once the 64 output channels are dealt to the MFMA rows in "paired-block order"
-//     (pm_acc_chan, common.h): lane (pixel i, quarter q) then holds the 8 consecutive channels of chunk 4k + q in the
-//     accumulators of blocks 2k and 2k+1, i.e. one whole 16-byte piece of the blocked layout.  Bias / ReLU / LeakyReLU(0.1) /
-//     residual add / activation-gradient mask / pixel-shuffle placement are applied in registers and every store (and
-//     residual / mask load) is a 16-byte-per-lane wave instruction over four 256-byte runs: 8 stores + 8 loads per wave and
-//     tile.  (r03: with 4 channels per lane = 16 + 16 eight-byte instructions, the vector-memory issue path, shared with
-//     the producers' 44 DMA pieces per tile, cost 1.2 k cycles per tile for the operand loads alone; with plain
-//     [pixel][64 ch] rows the stores hit 32 lines per instruction; an LDS transposition cost 2.7 k cycles per tile.)
-//     ReLU and the sign bits are computed on the PACKED bf16 words (v_pk_max_i16, v_pk_min_u16, v_lshl_or_b32: 1.5
-//     instructions per element instead of 4).
-#include "common.h"
+//   * ONE 512-thread workgroup per CU, grid = #CUs, persistent over 8x32-pixel tiles: 4 MFMA waves + 4 LDS-DMA producer waves, one of
+//     each per SIMD.  The packed weights (72 KiB) are loaded into LDS once and stay; the haloed input tile is double-buffered and
+//     filled one whole tile ahead; the residual / mask operands of the epilogue are requested into registers before the K loop.
+//     Nothing the tile needs is waited for at first use.
+//   * the LDS images, the weight staging, the producers' DMA, the K loop and the packed-word epilogue arms are the tile core this kernel
+//     shares with the chain kernel (conv3x3_chain.hip): conv3x3_c64_tile.h, described there.  Here: the tile walk, the launch's
+//     arguments, and the epilogue arms only a single layer needs (LeakyReLU(0.1), masks read from `aux`, pixel-shuffle placement).
+#include "conv3x3_c64_tile.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int PTW = 32, PTH = 8, PNT = 512;                              // 4 MFMA waves + 4 DMA waves
-constexpr int PTWH = PTW + 2, PTHH = PTH + 2, PNPIX = PTHH * PTWH;       // 34 x 10 = 340 haloed pixels
-constexpr int W_BYTES = 9 * 64 * 64 * 2;                                  // 73,728
-constexpr int IN_BYTES = PNPIX * 128;                                     // 43,520 per buffer
-constexpr int BIAS_OFF = W_BYTES + 2 * IN_BYTES;                          // 64 fp32 bias values behind the tiles
 constexpr int P_LDS = BIAS_OFF + 256;                                     // 161,024 <= 163,840
-constexpr int IN_CHUNKS = PNPIX * 8;                                      // 2,720 16-byte chunks
-constexpr int NPIECE_T = (IN_CHUNKS + 63) / 64;                           // 43 DMA pieces of 1 KiB (last half full)
-constexpr int NPIECE_W = (NPIECE_T + 3) / 4;                              // 11 per wave
 
 __device__ uint4 g_conv_zero_chunk[2];
 
@@ -87,28 +60,15 @@ struct TileIter {
     }
 };
 
-// two fp32 -> one dword of two bf16 (v_cvt_pk_bf16_f32), low half = a
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;     // a 16-byte piece (native vector: usable behind address-space pointers)
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    bf16x2_t p = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, p);
-}
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ unsigned pk_max_i16(unsigned a, unsigned b) { unsigned r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
 // Plain (not nt) tile DMA and output stores.  tools/bw_probe.hip streams reads at 6.4-7.0 TB/s with nt against 5.7-6.2 without, and
 // out of cache (tools/ab_conv.py, 8 rotating buffer sets) nt STORES took 7 % off a bias+ReLU launch (36.7 -> 34.0 us; bias+skip 42.3 ->
 // 41.5; nt loads: 36.2 / 44.3) -- but inside a step, applied to the outputs of >= 512 MB (the 16P tensors of the reconstruction), the
 // step was 0.2-0.7 ms SLOWER (124.6-124.9 -> 125.1-125.6 ms, three interleaved pairs): their consumers do find the tail of such a
 // tensor in the Infinity Cache (r04).
-#define GLDS16(src, dst)                                                                              \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
-                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
+constexpr int DMA_PLAIN = 0;
 
 // Epilogue variants are compile-time: a runtime-selected epilogue serialises 16 load->use->store
 // chains per tile (measured: 14 us of a 71 us launch).
@@ -132,17 +92,11 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
     asm volatile("" : "+s"(a.N), "+s"(a.H), "+s"(a.W), "+s"(a.Ws), "+s"(a.Wd), "+s"(a.in_step), "+s"(a.out_step), "+s"(a.src_ox0), "+s"(a.src_oy0),
                  "+s"(a.out_oxz), "+s"(a.out_oyz), "+s"(a.bias_zstride), "+s"(a.unshuffle), "+s"(a.src_nstride0), "+s"(a.dst_nstride), "+s"(a.w_zstride), "+s"(a.plane));
     asm volatile("" : "+s"(a.src0), "+s"(a.wpack), "+s"(a.resz), "+s"(a.auxz), "+s"(a.sign_bitsz), "+s"(a.dstz), "+s"(a.sign_outz), "+s"(a.bias), "+s"(a.leaky_slope));
-    // a pinned pointer comes back as an integer: name its address space, or hipcc addresses it with flat_ instructions
-#define GP(T, x) ((__attribute__((address_space(1))) T*)(x))
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int role = __builtin_amdgcn_readfirstlane(wave >> 2);            // 0: MFMA + epilogue, 1: LDS-DMA producer
     const int w4 = wave & 3;                                               // index within the role
     const int l15 = lane & 15, q = lane >> 4;                              // 16x16x32 operand / accumulator coordinates
-    // Pixel of a block that lane column l15 works on.  ds_read_b128 is serviced in lane groups {0-3,12-15,20-27}, {4-11,16-19,
-    // 28-31}, ... (MI355X_MICROARCH, LDS): a group mixes two channel chunks (q, q+1) whose images are 34 slots = 2 mod 16
-    // apart, so with pixel = l15 two of its 16 slots share banks (SQ_LDS_BANK_CONFLICT: 2 extra cycles per B read).  Lanes
-    // 4-11 on the even pixels and lanes 0-3, 12-15 on the odd ones make every group hit 16 distinct 16-byte bank groups.
-    const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
+    const int pxl = PM_LANE_PIXEL(l15);
     char* lds_w = smem;
     char* lds_t = smem + W_BYTES;                                         // two tile buffers
 #ifdef VSR_CLOCK
@@ -160,72 +114,26 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
     // (slot r = the channel MFMA row r of the 64 computes: paired-block order, see the epilogue)
     if (tid < 64) reinterpret_cast<float*>(smem + BIAS_OFF)[tid] = a.bias ? GP(const float, a.bias)[(long long)z * a.bias_zstride + pm_acc_chan(tid >> 4, tid & 15)] : 0.f;
 
-    // ---- weights of this z: global [tap][cout][cin] -> LDS, row r = MFMA row (block r >> 4, row r & 15) holds output channel
-    // pm_acc_chan(r >> 4, r & 15); chunk c of row r at (r*8 + (c ^ ((r>>1)&7))): the 16 rows a ds_read_b128 pass touches (same
-    // chunk, rows 16 mb .. 16 mb + 15) then fall on 16 distinct 16-byte bank groups ----
+    // ---- weights of this z -> LDS (C64_W_LOAD / C64_W_STORE) ----
     // The four MFMA waves stage all 4608 chunks (18 per thread; the loads are issued first, the waves' own set-up arithmetic runs
     // under their latency, then the LDS writes); the producer waves meanwhile do nothing but get the first tile's DMA out: at
     // the start of a launch the tile is the critical path (r03 stamps: the producers took 2.7 k cycles of set-up + 2.2 k of
     // issue + 3.2 k for their half of the weights before the first barrier; 8.4 k cycles of a 63 k-cycle launch).
-    constexpr int WCH = 9 * 64 * 8 / 256;                  // 18
     const auto* wg = GP(const u32x4_t, a.wpack + (unsigned long long)((long long)z * a.w_zstride) * 2);
-    // (written out in the MFMA branch: a register array handed to a lambda by reference goes through scratch memory)
-#define W_LOAD(wv)                                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < WCH; ++i) {                                                                    \
-        const int idx = tid + i * 256;                                                                                   \
-        const int tap = idx >> 9, r = (idx >> 3) & 63, c = idx & 7;                                                      \
-        wv[i] = wg[(tap * 64 + pm_acc_chan(r >> 4, r & 15)) * 8 + c];                                                    \
-    }
-#define W_STORE(wv)                                                                                                      \
-    _Pragma("unroll") for (int i = 0; i < WCH; ++i) {                                                                    \
-        const int idx = tid + i * 256;                                                                                   \
-        const int tap = idx >> 9, r = (idx >> 3) & 63, c = idx & 7;                                                      \
-        *reinterpret_cast<u32x4_t*>(lds_w + tap * 8192 + (r * 8 + (c ^ ((r >> 1) & 7))) * 16) = wv[i];                     \
-    }
 
     if (role == 1) {
         // =================== producer waves: LDS-DMA of the haloed tiles, one tile ahead ===================
         // Their VMEM issue slots (an LDS-DMA instruction does not finish issuing until the memory pipe takes it) run
-        // beside the MFMA waves' matrix-core time on the same SIMDs.  DMA pieces of this wave: piece = w4 + 4 i (64
-        // consecutive 16-byte LDS slots).  rel[i] = the source BYTE offset of this lane's slot (row ty, chunk c, pixel
-        // tx) from the tile origin in the blocked layout (tx0 is a multiple of 32: the 32 inner pixels of a row are one
-        // global segment, i.e. 512 contiguous bytes per chunk; the halo columns are the last / first pixel of the
-        // neighbouring segments).
+        // beside the MFMA waves' matrix-core time on the same SIMDs.
         const auto* src = GP(const char, a.src0);
         const auto* zsrc = GP(const char, g_conv_zero_chunk);
         int rel[NPIECE_W];
-#pragma unroll
-        for (int i = 0; i < NPIECE_W; ++i) {
-            const int idx = (w4 + 4 * i) * 64 + lane;           // LDS slot = [row ty][chunk c][34 pixels tx] x 16 B
-            const int ty = idx / (8 * PTWH), rem = idx - ty * (8 * PTWH);
-            const int c = rem / PTWH, tx = rem - c * PTWH;
-            // view pixel (ty-1, tx-1) is source pixel (v*in_step + src_o): in_step 2 = one pixel-shuffle phase of a
-            // twice-as-large tensor (the data gradient of conv3x3 + PixelShuffle, one launch per phase)
-            const int dx = (tx - 1) * a.in_step + a.src_ox0;
-            rel[i] = (((((ty - 1) * a.in_step + a.src_oy0) * WSs + (dx >> 5)) * 8 + c) * 256 + (dx & 31) * 8) * 2;
-        }
+        C64_DMA_REL(rel, w4, lane, a.in_step, a.src_oy0, a.src_ox0, WSs)
         auto issue = [&](const TileIter& it, int buf) {
             const int n = it.n, ty0 = it.ty * PTH, tx0 = it.tx * PTW;
             const auto* org = src + ((long long)n * a.src_nstride0 + pm_off(ty0 * a.in_step, tx0 * a.in_step, 0, a.Ws, 64)) * 2;
             char* dstb = lds_t + buf * IN_BYTES;
-            if (ty0 >= 1 && ty0 + PTH < a.H && tx0 >= 1 && tx0 + PTW < a.W) {          // interior tile (wave-uniform)
-#pragma unroll
-                for (int i = 0; i < NPIECE_W; ++i) {
-                    const int piece = w4 + 4 * i;
-                    if (piece < NPIECE_T && piece * 64 + lane < IN_CHUNKS) GLDS16(org + rel[i], dstb + piece * 1024);
-                }
-            } else {                                                                    // border: bounds per lane, zero source
-#pragma unroll
-                for (int i = 0; i < NPIECE_W; ++i) {
-                    const int piece = w4 + 4 * i;
-                    const int idx = piece * 64 + lane;
-                    const int ty = idx / (8 * PTWH), rem = idx - ty * (8 * PTWH);
-                    const int tx = rem % PTWH;
-                    const int vy = ty0 + ty - 1, vx = tx0 + tx - 1;
-                    const auto* s = (vy >= 0 && vy < a.H && vx >= 0 && vx < a.W) ? org + rel[i] : zsrc;
-                    if (piece < NPIECE_T && idx < IN_CHUNKS) GLDS16(s, dstb + piece * 1024);
-                }
-            }
+            C64_DMA_TILE(DMA_PLAIN, rel, org, zsrc, dstb, w4, lane, ty0, tx0, a.H, a.W)
         };
         int cur = 0;
         TileIter it;
@@ -242,21 +150,9 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
         }
     } else {
         // =================== MFMA waves: K loop + epilogue of tile rows 2 w4, 2 w4 + 1 ===================
-        // v_mfma_f32_16x16x32_bf16 (under MFMA load on random data the chip holds a higher clock on this shape than
-        // on 32x32x16, MI355X_MICROARCH "DVFS give-back" item 7): wave tile = 4 cout blocks x 4 pixel blocks (row,
-        // half) of 16; a step = one tap x 32 channels = 8 fragment reads (4 A + 4 B, ds_read_b128) + 16 MFMAs.
-        // Operand lane l = (i = l & 15, q = l >> 4): A[cout 16 mb + i][8 channels 8q..8q+7], B[same 8 channels][pixel i].
-        // Fragment addresses: A two lane bases per channel half (taps 0-5 / 6-8: the immediate is 16 bits) + immediates
-        // (tap, mb); B ONE lane base + immediates (row, ky, kx, half, channel half) of the [row][chunk][34 px][16 B] image.
         u32x4_t wv[WCH];
-        W_LOAD(wv)
-        unsigned a_lo[2], a_hi[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            a_lo[kk] = (unsigned)((l15 * 8 + ((4 * kk + q) ^ ((l15 >> 1) & 7))) * 16);
-            a_hi[kk] = a_lo[kk] + 6 * 8192;
-        }
-        const int b_lane = w4 * 2 * (PTWH * 128) + q * (PTWH * 16) + pxl * 16;
+        C64_W_LOAD(wv, wg, tid)
+        C64_MFMA_LANE(w4, l15, q, pxl)
         // epilogue: accumulator blocks (2k, nb) and (2k+1, nb), registers j = channels 8 (4k + q) + j and + 4 + j of pixel
         // (row nb >> 1, 16 (nb & 1) + i): chunk 4k + q of the blocked layout, whole.  loff[nb] = lane-constant part of the
         // destination element offset relative to the tile's origin pm_off(ty0*os + ooy, tx0*os) (tx0*os: multiple of 32)
@@ -270,7 +166,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                 loff[nb] = (int)(((row & 1) * 2 + (px & 1)) * a.plane) + (((row >> 1) * pm_ws(a.Wd >> 1)) * 8 + q) * 256 + (px >> 1) * 8;
             }
         }
-        W_STORE(wv)
+        C64_W_STORE(wv, lds_w, tid)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                   // weights and the first tile are in LDS
         auto* const dst_z = GP(bf16_t, a.dstz);
@@ -280,21 +176,10 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
         auto* const sout_z = GP(u32x2_t, a.sign_outz);
         const float slope = vsr_slope(a.leaky_slope);      // LeakyReLU slope (0.1 on the BasicVSR path, 0.2 in the discriminator)
 
-        // The bias of the wave's 16 rows per block (couts pm_acc_chan(mb, 4q + j)) stays in 16 registers and is the C operand of
-        // every accumulator's first MFMA: no per-tile initialisation (64 moves + 4 LDS reads per tile before).
         f32x4_t bvec[4];
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) bvec[mb] = *reinterpret_cast<const f32x4_t*>(smem + BIAS_OFF + (mb * 16 + 4 * q) * 4);
-        // The residual is added ON THE MATRIX CORES (r03): the 16-byte residual piece a lane prefetches (chunk 4k + q of its pixel) is
-        // exactly a B fragment of a K step over the 32 channels of pieces k, and "+ residual" is one more MFMA per accumulator with a
-        // 0 / 1 selection matrix as A: row r of block mb is channel pm_acc_chan(mb, r) = k group r >> 2, element 4 (mb & 1) + (r & 3) of
-        // that step.  16 MFMAs (256 cycles) replace 64 unpacks + 64 adds per tile and wave (512 issue cycles); fp32 accumulation of
-        // 1.0 x bf16 is the same single rounding as the v_add_f32 it replaces.
-        bf16x8_t idA[2];
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) idA[hb][j] = (bf16_t)((q == (l15 >> 2) && j == 4 * hb + (l15 & 3)) ? 1.f : 0.f);
+        for (int mb = 0; mb < 4; ++mb) bvec[mb] = c64_bias_rows(smem, q, mb);
+        C64_RES_IDENTITY(idA, l15, q)
         static_assert(!HAS_RES || ACT == ACT_NONE, "the residual goes in on the matrix cores, ahead of any activation");
 
         int cur = 0;
@@ -312,7 +197,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             constexpr bool LATE_MASK = HAS_RES && MASK != MASK_NONE && !BITS;   // both bf16 operands early would not fit 2 waves / SIMD
             u32x4_t rr[2][4], mm[2][4];                                // [k][nb]: 8 channels of one pixel
             u32x2_t sbits = {0u, 0u};                         // 64 sign bits of this lane's 64 outputs of the tile
-            if (BITS) sbits = sbits_z[(long long)tile * 256 + w4 * 64 + lane];
+            if (BITS) sbits = sbits_z[c64_sign_word(tile, w4, lane)];
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) ok[nb] = (tx0 + (nb & 1) * 16 + pxl < a.W) && (ty0 + w4 * 2 + (nb >> 1) < a.H);
 #define CV_OPERANDS(OKN)                                                                                               \
@@ -332,58 +217,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
 
             f32x4_t acc[4][4];                                      // first written by step 0's MFMAs, whose C operand is the bias
 
-            // ---- K loop: 18 steps s = (tap, channel half) of 16 MFMAs.  The 8 fragment reads of step s+1 are issued
-            // before the MFMAs of step s, by hand: lgkmcnt(8) = "all but the 8 youngest LDS reads have returned" = step s
-            // is in registers (hipcc sinks builtin LDS reads back in front of their consumers). ----
-            bf16x8_t fa[2][4], fb[2][4];
-            const unsigned bb = (unsigned)(W_BYTES + cur * IN_BYTES + b_lane);   // B base of this tile's buffer
-#define DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm))
-#define CV_LOADA(tap_, kk_, slot, mb)                                                                                  \
-            DSR(fa[slot][mb], (tap_ < 6 ? a_lo[kk_] : a_hi[kk_]), (tap_ < 6 ? tap_ : tap_ - 6) * 8192 + (mb) * 2048);
-#define CV_LOADB(ky_, kx_, kk_, slot, nb)                                                                              \
-            DSR(fb[slot][nb], bb, (((nb) >> 1) + ky_) * (PTWH * 128) + kk_ * (4 * PTWH * 16) + (((nb) & 1) * 16 + kx_) * 16);
-#define CV_LOAD(s, slot)                                                                                               \
-            {                                                                                                          \
-                constexpr int tap_ = (s) / 2, kk_ = (s) % 2, ky_ = tap_ / 3, kx_ = tap_ % 3;                           \
-                CV_LOADA(tap_, kk_, slot, 0) CV_LOADA(tap_, kk_, slot, 1) CV_LOADA(tap_, kk_, slot, 2) CV_LOADA(tap_, kk_, slot, 3) \
-                CV_LOADB(ky_, kx_, kk_, slot, 0) CV_LOADB(ky_, kx_, kk_, slot, 1) CV_LOADB(ky_, kx_, kk_, slot, 2) CV_LOADB(ky_, kx_, kk_, slot, 3) \
-            }
-#define CV_MFMA(s, mb, nb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[(s) % 2][mb], fb[(s) % 2][nb], (s) == 0 ? bvec[mb] : acc[mb][nb], 0, 0, 0);
-            // one fragment read of step s+1 behind each of the first 8 MFMAs of step s: the wave's LDS issue slots sit in
-            // the shadow of its own MFMAs, and the last read has 8 MFMAs (128 cycles) to return before step s+1 starts
-#define CV_ML_A(s, mb, nb, lmb)                                                                                        \
-            CV_MFMA(s, mb, nb)                                                                                         \
-            __builtin_amdgcn_sched_barrier(0);        /* hipcc would otherwise bunch the reads behind the MFMAs */       \
-            if ((s) + 1 < 18) { constexpr int t1_ = ((s) + 1) / 2, k1_ = ((s) + 1) % 2; CV_LOADA(t1_, k1_, ((s) + 1) % 2, lmb) } \
-            __builtin_amdgcn_sched_barrier(0);
-#define CV_ML_B(s, mb, nb, lnb)                                                                                        \
-            CV_MFMA(s, mb, nb)                                                                                         \
-            __builtin_amdgcn_sched_barrier(0);                                                                         \
-            if ((s) + 1 < 18) { constexpr int t1_ = ((s) + 1) / 2, k1_ = ((s) + 1) % 2; CV_LOADB(t1_ / 3, t1_ % 3, k1_, ((s) + 1) % 2, lnb) } \
-            __builtin_amdgcn_sched_barrier(0);
-#define CV_STEP(s)                                                                                                     \
-            {                                                                                                          \
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* step s is in registers */                   \
-                __builtin_amdgcn_sched_barrier(0);                                                                     \
-                CV_ML_A(s, 0, 0, 0) CV_ML_A(s, 0, 1, 1) CV_ML_A(s, 0, 2, 2) CV_ML_A(s, 0, 3, 3)                        \
-                CV_ML_B(s, 1, 0, 0) CV_ML_B(s, 1, 1, 1) CV_ML_B(s, 1, 2, 2) CV_ML_B(s, 1, 3, 3)                        \
-                CV_MFMA(s, 2, 0) CV_MFMA(s, 2, 1) CV_MFMA(s, 2, 2) CV_MFMA(s, 2, 3)                                    \
-                CV_MFMA(s, 3, 0) CV_MFMA(s, 3, 1) CV_MFMA(s, 3, 2) CV_MFMA(s, 3, 3)                                    \
-                __builtin_amdgcn_sched_barrier(0);                                                                     \
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // nothing of ours is outstanding
-            __builtin_amdgcn_sched_barrier(0);
-            CV_LOAD(0, 0)
-            CV_STEP(0) CV_STEP(1) CV_STEP(2) CV_STEP(3) CV_STEP(4) CV_STEP(5) CV_STEP(6) CV_STEP(7) CV_STEP(8)
-            CV_STEP(9) CV_STEP(10) CV_STEP(11) CV_STEP(12) CV_STEP(13) CV_STEP(14) CV_STEP(15) CV_STEP(16) CV_STEP(17)
-#undef CV_ML_A
-#undef CV_ML_B
-#undef CV_STEP
-#undef CV_MFMA
-#undef CV_LOAD
-#undef CV_LOADB
-#undef CV_LOADA
-#undef DSR
+            C64_K_LOOP(acc, bvec, cur)
 
             // ---- epilogue, entirely in registers; a store covers two 256-byte runs (two chunks x 16 pixels) per wave ----
             // The residual / mask operands were requested before the K loop and have long returned, but vmcnt counts loads and
@@ -392,17 +226,8 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             // per bias+skip launch).  One explicit wait here (the builtin: hipcc's scoreboard then knows the queue is empty)
             // covers the operands; the stores after it are never waited for inside the tile.
             if (HAS_RES || MASK != MASK_NONE) __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) alone
-            if constexpr (HAS_RES) {
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                    for (int mb = 0; mb < 4; ++mb)
-                        acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(idA[mb & 1], __builtin_bit_cast(bf16x8_t, rr[mb >> 1][nb]), acc[mb][nb], 0, 0, 0);
-            }
-            // Sign bits of the tile: the lane's 64 outputs are 32 packed words wd = (4k + nb) * 4 + jj (channels 2jj, 2jj+1 of the
-            // piece); word wd owns bits (wd & 15) [even channel] and 16 + (wd & 15) [odd channel] of sout[wd >> 4].
-            unsigned sout[2] = {0u, 0u};
-            const unsigned k11 = 0x00010001u;
+            if constexpr (HAS_RES) { C64_ADD_RESIDUAL(acc, idA, rr) }
+            unsigned sout[2] = {0u, 0u};                    // the lane's sign words (c64_tile.h)
             auto epilogue = [&](auto FULL) {
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
@@ -416,26 +241,17 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                         const unsigned wbits = k ? sbits.y : sbits.x;            // words wd = 16 k + 4 nb + jj
                         unsigned ow[4];
                         if (ACT == ACT_RELU && !HAS_RES && MASK == MASK_NONE) {
-                            // conv1 of a ResidualConv: round, then ReLU on the packed words (bf16 bit patterns order like int16
-                            // for this purpose: negative and -0 -> +0), sign bit = "the stored half is non-zero"
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) {
-                                ow[jj] = pk_max_i16(pk_bf16(v[2 * jj], v[2 * jj + 1]), 0u);
-                                sout[k] |= pk_min_u16(ow[jj], k11) << (4 * nb + jj);
-                            }
+                            C64_ARM_RELU(ow, v, nb, sout[k])       // conv1 of a ResidualConv
                         } else if (ACT == ACT_LEAKY && !HAS_RES && MASK == MASK_NONE) {
                             // conv_last.0: LeakyReLU = max(v, slope v) (0 < slope < 1), sign bits from the packed words as in the ReLU case
                             // (bit = "the stored half is positive", what sign_bits_c64_kernel computes from a stored activation)
 #pragma unroll
                             for (int jj = 0; jj < 4; ++jj) {
                                 ow[jj] = pk_bf16(fmaxf(v[2 * jj], v[2 * jj] * slope), fmaxf(v[2 * jj + 1], v[2 * jj + 1] * slope));
-                                sout[k] |= pk_min_u16(pk_max_i16(ow[jj], 0u), k11) << (4 * nb + jj);
+                                sout[k] |= pk_min_u16(pk_max_i16(ow[jj], 0u), C64_K11) << (4 * nb + jj);
                             }
                         } else if (ACT == ACT_NONE && !HAS_RES && MASK == MASK_RELU_BITS) {
-                            // dgrad(conv2) * ReLU': multiply the packed halves by their 0 / 1 bits
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj)
-                                ow[jj] = pk_mul_lo_u16(pk_bf16(v[2 * jj], v[2 * jj + 1]), (wbits >> (4 * nb + jj)) & k11);
+                            C64_ARM_MASKED(ow, v, nb, wbits)       // dgrad(conv2) * ReLU'
                         } else {
 #pragma unroll
                             for (int j = 0; j < 8; ++j) v[j] = p_act<ACT>(v[j], slope);
@@ -458,8 +274,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                                     v[2 * jj + 1] *= (bf_hi(mw[jj]) > 0.f ? 1.f : neg);
                                 }
                             }
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_bf16(v[2 * jj], v[2 * jj + 1]);
+                            C64_ARM_PLAIN(ow, v)
                         }
                         const u32x4_t o = {ow[0], ow[1], ow[2], ow[3]};
                         *GP(u32x4_t, dst + k * 1024) = o;
@@ -468,7 +283,7 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
             }
             };
             if (full) epilogue(std::true_type{}); else epilogue(std::false_type{});
-            if (ACT != ACT_NONE && !HAS_RES && sout_z) sout_z[(long long)tile * 256 + w4 * 64 + lane] = u32x2_t{sout[0], sout[1]};
+            if (ACT != ACT_NONE && !HAS_RES && sout_z) sout_z[c64_sign_word(tile, w4, lane)] = u32x2_t{sout[0], sout[1]};
             __syncthreads();                               // the producers' next tile has landed; everybody has finished reading `cur`
             cur ^= 1;
         }
@@ -493,7 +308,7 @@ __global__ void sign_bits_c64_kernel(const bf16_t* __restrict__ x, uint2* __rest
     const int lane = (int)(gid & 63), w4 = (int)((gid >> 6) & 3);
     const int tile = (int)(gid >> 8);
     const int l15 = lane & 15, q = lane >> 4;
-    const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
+    const int pxl = PM_LANE_PIXEL(l15);
     int n, ty0, tx0;
     tile_coords(tile, ntx, nty, n, ty0, tx0);
     unsigned out[2] = {0u, 0u};

@@ -18,14 +18,13 @@
 //     (k groups 0-1 = tap kx, 2-3 = tap kx + 1; the 8th tap of a row has zero weights), 28 instead of 49 steps.
 //   * epilogue as in the 3x3 kernel: bias is the accumulators' initial value, ReLU on the packed bf16 words, 16-byte stores in
 //     paired-block channel order (pm_acc_chan); the 2-channel flow layer stores planar fp32 (+ the upsampled flow, spynet.py:65).
-#include "common.h"
+#include "conv3x3_c64_tile.h"      // the packed-word helpers pk_*
 
 namespace {
 
 constexpr int QTW = 32, QTH = 8, QNT = 512, QHALO = 3;
 constexpr int QTHH = QTH + 2 * QHALO;                  // 14 haloed rows
 
-typedef __attribute__((ext_vector_type(2))) __bf16 qbf16x2_t;
 typedef __attribute__((ext_vector_type(4))) unsigned qu32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned qu32x2_t;
 
@@ -36,16 +35,9 @@ __device__ uint4 g_c7_zero_chunk[2];
 __device__ unsigned long long g_clk7[256 * 4];
 #endif
 
-__device__ __forceinline__ unsigned q_pk_bf16(float a, float b) {
-    qbf16x2_t p = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ unsigned q_pk_max_i16(unsigned a, unsigned b) { unsigned r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned q_pk_min_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned q_pk_mul_lo_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // ReLU' of a stored bf16 activation applied to a packed pair: both halves times (activation > 0) (bf16 patterns order like int16
-// for this purpose, see conv3x3_persist.hip)
-__device__ __forceinline__ unsigned q_relu_mask(unsigned v, unsigned act) { return q_pk_mul_lo_u16(v, q_pk_min_u16(q_pk_max_i16(act, 0u), 0x00010001u)); }
+// for this purpose, see conv3x3_c64_tile.h)
+__device__ __forceinline__ unsigned q_relu_mask(unsigned v, unsigned act) { return pk_mul_lo_u16(v, pk_min_u16(pk_max_i16(act, 0u), 0x00010001u)); }
 
 #define QGLDS16(src, dst)                                                                             \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),            \
@@ -126,8 +118,7 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
     unsigned long long clk_t0 = 0, clk_r0 = 0;
     if (tid == 0) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
-    // pixel of a 16-pixel block that lane column l15 works on (bank-conflict-free B reads for any even row pitch: see the 3x3 kernel)
-    const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
+    const int pxl = PM_LANE_PIXEL(l15);         // bank-conflict-free B reads for any even row pitch
 
     const int ntx = cdiv(a.W, QTW), nty = cdiv(a.H, QTH);
     const int total = a.N * ntx * nty;
@@ -382,18 +373,18 @@ __global__ __launch_bounds__(QNT, 1) void conv7x7_persist_kernel(const ConvArgs 
                         if (OKN) {                                                                                     \
                             auto* d = dstp + tbase + loff[nb];                                                         \
                             if constexpr (NB == 1) {                                                                   \
-                                unsigned o0 = q_pk_bf16(acc[0][nb][0], acc[0][nb][1]), o1 = q_pk_bf16(acc[0][nb][2], acc[0][nb][3]); \
-                                if (relu) { o0 = q_pk_max_i16(o0, 0u); o1 = q_pk_max_i16(o1, 0u); }                    \
+                                unsigned o0 = pk_bf16(acc[0][nb][0], acc[0][nb][1]), o1 = pk_bf16(acc[0][nb][2], acc[0][nb][3]); \
+                                if (relu) { o0 = pk_max_i16(o0, 0u); o1 = pk_max_i16(o1, 0u); }                    \
                                 if (a.aux) { o0 = q_relu_mask(o0, mm[0][nb].x); o1 = q_relu_mask(o1, mm[0][nb].y); }    \
                                 if ((q >> 1) < CDc) *QGP(qu32x2_t, d) = qu32x2_t{o0, o1};                              \
                             } else {                                                                                   \
                                 _Pragma("unroll") for (int k = 0; k < NB / 2; ++k) {                                   \
                                     unsigned ow[4];                                                                    \
                                     _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                 \
-                                        ow[jj] = q_pk_bf16(acc[2 * k][nb][2 * jj], acc[2 * k][nb][2 * jj + 1]);        \
-                                        ow[2 + jj] = q_pk_bf16(acc[(2 * k + 1) & (NB - 1)][nb][2 * jj], acc[(2 * k + 1) & (NB - 1)][nb][2 * jj + 1]); \
+                                        ow[jj] = pk_bf16(acc[2 * k][nb][2 * jj], acc[2 * k][nb][2 * jj + 1]);        \
+                                        ow[2 + jj] = pk_bf16(acc[(2 * k + 1) & (NB - 1)][nb][2 * jj], acc[(2 * k + 1) & (NB - 1)][nb][2 * jj + 1]); \
                                     }                                                                                  \
-                                    if (relu) { _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) ow[jj] = q_pk_max_i16(ow[jj], 0u); } \
+                                    if (relu) { _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) ow[jj] = pk_max_i16(ow[jj], 0u); } \
                                     if (a.aux) { ow[0] = q_relu_mask(ow[0], mm[k][nb].x); ow[1] = q_relu_mask(ow[1], mm[k][nb].y);  \
                                                  ow[2] = q_relu_mask(ow[2], mm[k][nb].z); ow[3] = q_relu_mask(ow[3], mm[k][nb].w); } \
                                     if (4 * k + q < CDc) *QGP(qu32x4_t, d + k * 1024) = qu32x4_t{ow[0], ow[1], ow[2], ow[3]}; \

@@ -333,7 +333,7 @@ __global__ __launch_bounds__(W2_NT, 1) void conv_wide2_kernel(const Wide2Args a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pg = wave & 3, ch = wave >> 2;
     const int l15 = lane & 15, q = lane >> 4;
-    const int pxl = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);   // as conv3x3_persist
+    const int pxl = PM_LANE_PIXEL(l15);
     char* lds_w = smem;
     char* lds_t = smem + 3 * W2_WSLAB;
 

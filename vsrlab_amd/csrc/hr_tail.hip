@@ -1,6 +1,7 @@
 // conv_last.2 (basicvsr.py:21: conv3x3 64 -> 3 at 4h x 4w) has 3 real output channels: its backward is a
 // streaming problem, not a GEMM.  Dedicated bf16 kernels for the HR tail of the backward pass (the generic tiled
 // kernel pads 3 channels to 16/32 and synchronises per tap: 0.9 ms per frame at 2160x3840 against an HBM floor of ~0.45).
+#include "conv3x3_c64_tile.h"      // c64_sign_word: the sign bits are read in the 3x3 kernels' tile order
 #include "kernels.h"
 #include <type_traits>
 
@@ -45,8 +46,7 @@ __global__ __launch_bounds__(LT_NT) void last2_dgrad_kernel(const float* __restr
     __shared__ float tile[2][3 * LT_PL];
     const int tid = threadIdx.x, lane = tid & 63, w4 = tid >> 6;
     const int l15 = lane & 15, q = lane >> 4;
-    // pixel of a 16-pixel block that lane column l15 works on: the persistent conv kernel's permutation (conv3x3_persist.hip)
-    const int i15 = (l15 >= 4 && l15 < 12) ? 2 * (l15 - 4) : (l15 < 4 ? 2 * l15 + 1 : 2 * (l15 - 8) + 1);
+    const int i15 = PM_LANE_PIXEL(l15);         // the persistent conv kernels' permutation
     const int ntx = cdiv(W, LT_W), nty = cdiv(H, LT_H);
     const int total = N * ntx * nty;
     const long long plane = (long long)H * W;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(LT_NT) void last2_dgrad_kernel(const float* __restr
         typedef __attribute__((ext_vector_type(2))) unsigned sb2_t;
         sb2_t sbv = {0u, 0u};
         if (MODE == 2) {
-            const auto* sp = (const __attribute__((address_space(1))) sb2_t*)(sign_bits + ((long long)t * 256 + w4 * 64 + lane));
+            const auto* sp = (const __attribute__((address_space(1))) sb2_t*)(sign_bits + c64_sign_word(t, w4, lane));
             asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(sbv) : "v"(sp) : "memory");
         }
         const int tn = t + gridDim.x;

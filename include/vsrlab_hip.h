@@ -388,6 +388,27 @@ int vsr_deform_conv_bwd(const VsrDeformDesc* d, const float* x, const float* off
 /* the flow-guided epilogue on its own (flow_guided = 1): offset and mask as the fused calls form them, bit for bit */
 int vsr_deform_offset_mask(const VsrDeformDesc* d, const float* out, const float* flow, float* offset, float* mask, void* stream);
 
+/* ---- PSNR and SSIM in one pass (csrc/metrics.hip) ---------------------------------------------------
+ * piqa.PSNR / piqa.SSIM as the reference's `metric:` blocks configure them (conf/train/default.yaml:8-14), fed by
+ * compute_metric (core/utils.py:242-252).  x (prediction) and y (target): `planes` = N*C fp32 planes of H x W, planar.
+ * SSIM: Gaussian window of window_size taps (odd, 3..15; the taps are computed on the host in fp32 from sigma), no padding,
+ * so ss has (H - window_size + 1) x (W - window_size + 1) values per plane; c1 = (k1 * value_range)^2, c2 = (k2 * value_range)^2.
+ * clamp_x != 0: x is clamped to [clamp_lo, clamp_hi] as it is loaded (compute_metric's sr.clamp(0, 1)); y never is.
+ * sums (device, fp64, N x 2) = per image the sum of ss over its C planes and the sum of (x - y)^2 over all its C*H*W pixels:
+ * the caller divides, so a batch split into chunks gives the same per-image bits.  Both are reduced in a fixed order
+ * (no atomics): two calls give identical bits.  H or W below window_size, an even window or one outside 3..15 is
+ * VSR_STATUS_UNSUPPORTED (scratch query: 0).  scratch: device memory of the queried size, owned by the call until it finished. */
+typedef struct VsrMetricsDesc {
+    long long planes;          /* N*C */
+    int C, H, W;
+    int window_size;           /* odd, 3..15 */
+    float sigma, c1, c2;
+    int clamp_x; float clamp_lo, clamp_hi;
+} VsrMetricsDesc;
+size_t vsr_metrics_scratch_bytes(const VsrMetricsDesc* d);       /* 0: unsupported descriptor */
+int vsr_psnr_ssim(const VsrMetricsDesc* d, const float* x, const float* y, double* sums, void* scratch, size_t scratch_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,12 @@ class DeformDesc(ctypes.Structure):
                [("max_residue", c_float), ("dtype", c_int)]
 
 
+class MetricsDesc(ctypes.Structure):
+    """struct VsrMetricsDesc (include/vsrlab_hip.h)."""
+    _fields_ = [("planes", c_longlong), ("C", c_int), ("H", c_int), ("W", c_int), ("window_size", c_int),
+                ("sigma", c_float), ("c1", c_float), ("c2", c_float), ("clamp_x", c_int), ("clamp_lo", c_float), ("clamp_hi", c_float)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -107,6 +113,8 @@ _SIGNATURES = {
     "vsr_deform_conv_fwd": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "vsr_deform_conv_bwd": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "vsr_deform_offset_mask": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P]),
+    "vsr_metrics_scratch_bytes": (c_size_t, [ctypes.POINTER(MetricsDesc)]),
+    "vsr_psnr_ssim": (c_int, [ctypes.POINTER(MetricsDesc), _P, _P, _P, _P, c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -19,9 +19,28 @@ def install_as_vsrlab(force: bool = False) -> None:
                 "vsr.models.RealBasicVSR.modules.basicvsr", "vsr.models.RealBasicVSR.modules.spynet",
                 "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.modules",
                 "vsr.models.VRT.modules.spynet", "vsr.models.VRT.modules.window_attention", "vsr.models.VRT.modules.tmsa", "vsr.models.VRT.modules.deform_conv",
-                "core.utils", "train_gan", "optical_flow",
+                "core.utils", "core.metrics", "train_gan", "optical_flow",
                 "optical_flow.models", "optical_flow.models.spynet"):
         sys.modules["vsrlab." + sub] = importlib.import_module("vsrlab_amd." + sub)
+
+
+def install_metrics_as_piqa() -> bool:
+    """Opt-in: make ``_target_: piqa.PSNR`` / ``piqa.SSIM`` (conf/train/default.yaml:8-14) resolve to ``vsrlab_amd.core.metrics``
+    on a host WITHOUT piqa, by registering a module named ``piqa`` that exposes those two classes and nothing else.  Where the
+    real piqa can be imported nothing is registered and False is returned; nothing in this package calls this function."""
+    import types
+    from importlib.util import find_spec
+    from .core import metrics
+    present = sys.modules.get("piqa")
+    if present is not None:
+        return getattr(present, "PSNR", None) is metrics.PSNR
+    if find_spec("piqa") is not None:
+        return False
+    mod = types.ModuleType("piqa")
+    mod.__doc__ = "vsrlab_amd.core.metrics under piqa's name (vsrlab_amd.compat.install_metrics_as_piqa)"
+    mod.PSNR, mod.SSIM = metrics.PSNR, metrics.SSIM
+    sys.modules["piqa"] = mod
+    return True
 
 
 def instantiate(cfg: dict):

@@ -8,6 +8,10 @@
   (``vsrlab_amd.parallel.FlatGradSync``) exchanges gradients once per optimizer step (``no_sync`` semantics on the
   accumulation micro-steps).  With any other optimizer it does exactly what the reference does.
 
+* ``compute_metric`` / ``running_metrics`` (``core/utils.py:242-252``): the metric collection on the clamped prediction.  The
+  clamp runs inside the metric kernel (``MetricCollection.forward(..., clamp=(0, 1))``) and a contiguous clip is viewed, not
+  copied, as (b t) c h w.
+
 The harness around them (Hydra, loggers, data loading, checkpoint I/O) is out of scope.
 """
 from __future__ import annotations
@@ -43,6 +47,25 @@ def compute_loss(loss_fn, sr, hr, lq=None):
         _, _, c, h, w = lq.size()
         loss = loss + loss_fn(lq, resize(hr, (h, w)))
     return loss
+
+
+def compute_metric(metric, sr, hr):
+    """Reference ``compute_metric`` (core/utils.py:242-247): ``metric`` on ``sr.detach().clamp(0, 1)`` and ``hr.detach()``, both
+    (b, t, c, h, w) flattened to ((b t), c, h, w).  A ``vsrlab_amd.core.metrics.MetricCollection`` gets the clamp as a keyword and
+    fuses it into its kernel; any other callable gets the clamped tensor, as in the reference."""
+    from .metrics import MetricCollection
+    b, t, c, h, w = sr.shape
+    x, y = sr.detach().reshape(b * t, c, h, w), hr.detach().reshape(b * t, c, h, w)
+    if isinstance(metric, MetricCollection):
+        return metric(x, y, clamp=(0.0, 1.0))
+    return metric(x.clamp(0, 1), y)
+
+
+def running_metrics(metrics_dict, metric, sr, hr):
+    """Reference ``running_metrics`` (core/utils.py:249-252): this batch's metrics added to the running sums, for the keys that
+    both have; a key that only one of them has is dropped."""
+    batch = compute_metric(metric, sr, hr)
+    return {key: total + batch[key] for key, total in metrics_dict.items() if key in batch}
 
 
 def update_weights(model, loss, scaler, scheduler, optimizer, num_grad_acc, grad_clip, i, grad_sync=None):

@@ -45,7 +45,7 @@ extern "C" {
 int vsr_abi_version(void);
 const char* vsr_status_string(int status);
 
-/* ---- whole-path engine -------------------------------------------------------------------
+/* ---- whole-path engine (csrc/engine.hip) ---------------------------------------------------
  * Replaces BasicVSR.forward and its autograd backward (basicvsr.py:39-83).
  * mid_channels must be 64 (the reference's default, basicvsr.py:12-13) for the vsr_basicvsr_* entries; the
  * narrow widths 16 and 32 have an entry family of their own (vsr_basicvsr_narrow_*, below: same descriptor,
@@ -122,7 +122,7 @@ int vsr_basicvsr_narrow_backward(const VsrBasicVSRDesc* d, const float* const* p
 int vsr_basicvsr_narrow_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward,
                                   float* flow_backward, void* stream);
 
-/* ---- SPyNet alone: flow = Spynet(ref, supp)  (RealBasicVSR/modules/spynet.py:69-93) -------
+/* ---- SPyNet alone: flow = Spynet(ref, supp)  (RealBasicVSR/modules/spynet.py:69-93; csrc/spynet_engine.hip) -------
  * ref/supp (N,3,h,w) fp32 planar; params: the 62 spynet tensors in state_dict order.        */
 size_t vsr_spynet_workspace_bytes(int N, int h, int w, int dtype, int need_backward);
 int vsr_spynet_forward(int N, int h, int w, int dtype, const float* const* params, int nparams,
@@ -150,7 +150,7 @@ int vsr_spynet_backward_ex(int N, int h, int w, int dtype, const float* const* p
                            const float* dflow, int last_relu, const float* const* dlevel, float* dref, float* dsupp,
                            void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- RealBasicVSR pre-clean stack, forward: lq = IterativeRefinement(lr) ----------------------
+/* ---- RealBasicVSR pre-clean stack, forward: lq = IterativeRefinement(lr)  (csrc/cleaner_engine.hip) ----------------------
  * (vsr/models/RealBasicVSR/realbasicvsr.py:17-30): `steps` times x <- x + conv(ResidualBlock(x)) on
  * the F = n*t frames (F,3,h,w) fp32 planar.  params (4 + 4*blocks tensors): resblock.conv.0.{weight,
  * bias}, resblock.res_block.{i}.conv1.{weight,bias}, conv2.{weight,bias} ..., conv.{weight,bias}.
@@ -171,7 +171,7 @@ int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int 
                          float* const* grads, int nparams, const float* lr, const float* dlq, float* dlr,
                          void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- per-op entry points (pixel-major tensors) --------------------------------------------- */
+/* ---- per-op entry points (pixel-major tensors; csrc/layer_ops.hip) ------------------------- */
 /* flow_warp, zeros padding (spynet.py:95-106): out[n,y,x,:] = bilinear(in[n], x+fx, y+fy)     */
 int vsr_flow_warp_fwd(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H,
                       int W, int C, void* stream);

@@ -7,69 +7,10 @@
 // of the clip is retained, so each layer's weight gradient is ONE split-K launch over all t frames
 // (see wgrad_mfma.hip) instead of t launches + t reductions.
 #include <vector>
-#include "host.h"
+#include "recipes.h"
+#include "spynet_engine.h"
 
 namespace {
-
-constexpr int C = 64;           // mid channels of the HIP path (the narrow entries run 16 / 32: Plan::C shadows this in the engine)
-constexpr int NSPY = 5;         // convs per SPyNet level
-const int SPY_CI[NSPY] = {8, 32, 64, 32, 16}, SPY_CO[NSPY] = {32, 64, 32, 16, 2};
-const int SPY_CIP[NSPY] = {16, 32, 64, 32, 16}, SPY_COP[NSPY] = {32, 64, 32, 32, 32};   // padded (template) sizes
-const int SPY_CD[NSPY] = {32, 64, 32, 16, 0};     // channels per pixel of each layer's pixel-major output
-// backward (train_flow): pixel-major channels of each layer's dY, and the dgrad launch's template rows (COUT)
-const int SPY_DK[NSPY] = {32, 64, 32, 16, 16}, SPY_DROWS[NSPY] = {32, 32, 64, 32, 32};
-
-struct SpyPlan {
-    int P = 0, F = 0, h = 0, w = 0, hu = 0, wu = 0;
-    size_t pyr[6] = {};          // planar fp32 normalised frames, level 0 = coarsest
-    size_t x16 = 0, b32a = 0, b64 = 0, b32b = 0, b16 = 0;   // pixel-major T at the finest level size
-    size_t flow_a = 0, flow_b = 0, flow_up = 0;     // planar fp32 [P][2][hu][wu]
-    size_t wpack[6][NSPY] = {}, bias[6][NSPY] = {};
-    // train_flow (need_backward = 2): per-level saved activations, dgrad weights and backward scratch
-    bool save = false;
-    size_t sx[6][NSPY] = {};                 // inputs of the 5 convs of each level: x16, b32a, b64, b32b, b16
-    size_t sfup[6] = {}, sres[6] = {};            // planar fp32 flow_up and residue (= ReLU(conv5)) per level
-    size_t wpackd[6][NSPY] = {};
-    size_t gA = 0, gB = 0, dres = 0, dfa = 0, dfb = 0;
-    size_t dpyr[6] = {};                     // gradient of the normalised pyramid (input-frame gradient)
-    void plan_save(Bump& b, int dtype) {
-        save = true;
-        const size_t es = esize(dtype);
-        for (int l = 0; l < 6; ++l) {
-            const int hl = hu >> (5 - l), wl = wu >> (5 - l);
-            for (int j = 0; j < NSPY; ++j) sx[l][j] = b.take((size_t)P * pm_image_elems(hl, wl, SPY_CIP[j]) * es);
-            sfup[l] = b.take((size_t)P * 2 * hl * wl * 4);
-            sres[l] = b.take((size_t)P * 2 * hl * wl * 4);
-            for (int j = 0; j < NSPY; ++j) wpackd[l][j] = b.take((size_t)49 * 64 * 64 * es);
-        }
-        gA = b.take((size_t)P * pm_image_elems(hu, wu, 64) * es);
-        gB = b.take((size_t)P * pm_image_elems(hu, wu, 64) * es);
-        dres = b.take((size_t)P * pm_image_elems(hu, wu, 16) * es);
-        dfa = b.take((size_t)P * 2 * hu * wu * 4);
-        dfb = b.take((size_t)P * 2 * hu * wu * 4);
-        for (int l = 0; l < 6; ++l) dpyr[l] = b.take((size_t)F * 3 * (hu >> (5 - l)) * (wu >> (5 - l)) * 4);
-    }
-    void plan(Bump& b, int P_, int F_, int h_, int w_, int dtype) {
-        P = P_; F = F_; h = h_; w = w_;
-        wu = (w % 32) == 0 ? w : 32 * (w / 32 + 1);      // spynet.py:72-73
-        hu = (h % 32) == 0 ? h : 32 * (h / 32 + 1);
-        const size_t es = esize(dtype);
-        for (int l = 0; l < 6; ++l) {
-            const int s = 5 - l;
-            pyr[l] = b.take((size_t)F * 3 * (hu >> s) * (wu >> s) * 4);
-        }
-        const size_t px = (size_t)P * hu * wu;
-        auto pm = [&](int Cc) { return (size_t)P * pm_image_elems(hu, wu, Cc) * es; };     // blocked pixel-major tensors
-        x16 = b.take(pm(16)); b32a = b.take(pm(32)); b64 = b.take(pm(64));
-        b32b = b.take(pm(32)); b16 = b.take(pm(16));
-        flow_a = b.take(px * 2 * 4); flow_b = b.take(px * 2 * 4); flow_up = b.take(px * 2 * 4);
-        for (int l = 0; l < 6; ++l)
-            for (int j = 0; j < NSPY; ++j) {
-                wpack[l][j] = b.take((size_t)49 * SPY_COP[j] * SPY_CIP[j] * es);
-                bias[l][j] = b.take(64 * 4);
-            }
-    }
-};
 
 struct Plan {
     VsrBasicVSRDesc d = {};
@@ -258,215 +199,6 @@ struct Plan {
     }
 };
 
-// What every launch recipe needs: the stream, the compute dtype, the mid-channel width and (backward) this stream's weight-gradient
-// slab buffer.  The engines address their arena through at() / fat(); the per-op entries (ws = null) run the same recipes on the
-// caller's buffers.
-struct Ctx {
-    char* ws;
-    hipStream_t st;
-    int dtype;
-    // mid channels: 64 (persistent kernels, sign bits, phase planes) or 16 / 32 (one generic-kernel launch per layer); CO: the conv
-    // template's output rows for C outputs (C = 16 runs on the 32-row template with cout_real = 16)
-    int C, CO;
-    size_t es;
-    float* slab;                // wgrad_slab_bytes() for the weight-gradient partials of this stream (null: no backward)
-    mutable std::vector<VsrPackDesc>* batch = nullptr;      // while set, pack() collects descriptors for ONE multi-tensor launch
-    Ctx(char* ws_, hipStream_t st_, int dtype_, int C_ = 64, float* slab_ = nullptr)
-        : ws(ws_), st(st_), dtype(dtype_), C(C_), CO(C_ < 32 ? 32 : C_), es(esize(dtype_)), slab(slab_) {}
-    void* at(size_t off) const { return ws + off; }
-    const float* fat(size_t off) const { return reinterpret_cast<const float*>(ws + off); }
-
-    // the destination of `a` (an N x H x W x 64 image, H and W even) as four phase planes of N x H/2 x W/2 x 64 (ConvArgs::unshuffle)
-    static long long plane_elems(int N, int H, int W) { return (long long)N * pm_image_elems(H / 2, W / 2, 64); }
-    static void set_unshuffle(ConvArgs& a, int N, int H, int W) {
-        a.unshuffle = 1; a.unshuffle_plane = plane_elems(N, H, W); a.dst_nstride = pm_image_elems(H / 2, W / 2, 64);
-    }
-    // y = act(conv(x) + bias) (+res) (*mask(aux)) -- C -> C, 3x3 or 1x1, at one resolution (bf16 3x3 at C = 64: the persistent
-    // kernel; sign bits and phase-separated outputs exist there only)
-    int conv(int ks, const void* x, const void* wpack, const float* bias, void* y, int act, const void* res, const void* aux, int mask,
-             int N, int H, int W, void* sign_out = nullptr, const void* sign_bits = nullptr, bool unshuffle = false, float slope = 0.f) const {
-        ConvArgs a = conv_args(N, H, W, C);
-        a.src[0] = x; a.wpack = wpack; a.bias = bias; a.dst[0] = y; a.act = act; a.leaky_slope = slope; a.res[0] = res; a.aux[0] = aux; a.mask_mode = mask;
-        a.sign_out[0] = sign_out; a.sign_bits[0] = sign_bits;
-        if (unshuffle) set_unshuffle(a, N, H, W);
-        const int rc = vsr_launch_conv(dtype, ks, 1, C, C, 0, CO, EPI_NHWC, a, st);
-        // VSRLAB_AMD_GENERIC_CONV=1 (A/B switch): the generic kernel does not write sign bits, but later launches (hr_tail.hip's
-        // conv_last.2 data gradient, the masked data gradients) read them -- r04: the switch gave wrong gradients since round 2
-        if (rc == VSR_OK && sign_out && dtype == VSR_BF16 && vsr_env().generic_conv) return vsr_launch_sign_bits_c64(y, sign_out, N, H, W, st);
-        return rc;
-    }
-    // C -> 3 planar fp32 (+ pres): the stems' LR-channel gradient, the pre-clean out conv
-    int conv_planar3(const void* x, const void* wpack, const float* bias, float* y, long long y_nstride, const float* pres, int N, int H, int W) const {
-        ConvArgs a = conv_args(N, H, W, C);
-        a.src[0] = x; a.wpack = wpack; a.bias = bias; a.cout_real = 3; a.dst[0] = y; a.dst_nstride = y_nstride; a.pres = pres;
-        return vsr_launch_conv(dtype, 3, 1, C, C, 0, 32, EPI_PLANAR, a, st);
-    }
-
-    // ---- PixelShufflePack (upsampling.py:4-12) ----
-    // PixelShuffle(2): out[c, 2y+i, 2x+j] = conv[4c+2i+j, y, x]  => sub-conv z uses rows 4c+z and bias entries 4c+z
-    int pack_ps(const float* w, void* dst, int mode) const {
-        for (int z = 0; z < 4; ++z) CK(pack(w, (char*)dst + (size_t)z * 9 * CO * C * es, 9, CO, C, C, C, C, 0, 4, z, mode));
-        return VSR_OK;
-    }
-    int pack_ps_bias(const float* b, float* dst) const {
-        for (int z = 0; z < 4; ++z) CK(pack_bias(b, dst + z * C, C, 4, z));
-        return VSR_OK;
-    }
-    // conv3x3 C->4C + PixelShuffle(2): x (N,H,W,C) -> y (N,2H,2W,C)   (upsampling.py:10-12)
-    int conv_ps(const void* x, const void* wpack, const float* bias4, void* y, int N, int H, int W, int act = ACT_NONE, float slope = 0.f) const {
-        ConvArgs a = conv_args(N, H, W, C);
-        a.src[0] = x; a.wpack = wpack; a.w_zstride = 9 * CO * C; a.bias = bias4; a.bias_zstride = C; a.nz = 4; a.act = act; a.leaky_slope = slope;
-        a.out_step = 2; a.Hd = 2 * H; a.Wd = 2 * W; a.dst_nstride = pm_image_elems(2 * H, 2 * W, C);
-        for (int z = 0; z < 4; ++z) { a.dst[z] = y; a.out_oy[z] = z >> 1; a.out_ox[z] = z & 1; }
-        return vsr_launch_conv(dtype, 3, 1, C, C, 0, CO, EPI_NHWC, a, st);
-    }
-    // data gradient of the above: dy (N,2H,2W,64) -> dx (N,H,W,64) (* mask(aux)) = sum over the 4 pixel-shuffle
-    // phases z of a transposed 3x3 64->64 conv of dy's phase z.  bf16: four launches of the persistent kernel (the
-    // four weight sets do not fit LDS together), phase z reading phase z-1's partial sum as its residual in place --
-    // the partial sums pass through bf16 three times (~1.6x the rounding error of the final store alone), for
-    // 560 us instead of 1470 us at 1080x1920.  fp32: one generic 4-source launch, accumulated in registers.
-    // dy_planes: dy is stored phase-separated (four N x H x W planes, written by a launch with ConvArgs::unshuffle): phase z is then a
-    // contiguous tensor instead of every second pixel of every second row of the 2H x 2W image (r04: the strided form fetched every
-    // line of dy twice per data gradient and again twice per weight gradient); dx_planes: write dx phase-separated in turn.
-    // C < 64: the one 4-source launch in both dtypes (the persistent kernel is 64-channel).
-    int conv_ps_dgrad(const void* dy, const void* wpackd, void* dx, const void* aux, int mask, int N, int H, int W, const void* sign_bits = nullptr,
-                      bool dy_planes = false, bool dx_planes = false) const {
-        if (dtype == VSR_BF16 && C == 64) {
-            for (int z = 0; z < 4; ++z) {
-                ConvArgs a = conv_args(N, H, W, C);
-                if (dy_planes) {
-                    a.src[0] = (const char*)dy + (size_t)z * plane_elems(N, 2 * H, 2 * W) * es;      // plane z: N x H x W, stride 1 (conv_args() set it up)
-                } else {
-                    a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
-                    a.src[0] = dy; a.src_oy[0] = z >> 1; a.src_ox[0] = z & 1; a.src_nstride[0] = pm_image_elems(2 * H, 2 * W, C);
-                }
-                a.wpack = (const char*)wpackd + (size_t)z * 9 * C * C * es; a.dst[0] = dx;
-                a.res[0] = z > 0 ? dx : nullptr;
-                if (dx_planes) set_unshuffle(a, N, H, W);
-                if (z == 3) { a.aux[0] = aux; a.mask_mode = mask; a.sign_bits[0] = aux ? sign_bits : nullptr; }
-                int rc = vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
-                if (rc != VSR_OK) return rc;
-            }
-            return VSR_OK;
-        }
-        ConvArgs a = conv_args(N, H, W, C);
-        a.nz = 1; a.in_step = 2; a.Hs = 2 * H; a.Ws = 2 * W;
-        for (int s = 0; s < 4; ++s) { a.src[s] = dy; a.src_oy[s] = s >> 1; a.src_ox[s] = s & 1; a.src_nstride[s] = pm_image_elems(2 * H, 2 * W, C); }
-        a.wpack = wpackd; a.dst[0] = dx; a.aux[0] = aux; a.mask_mode = mask;
-        return vsr_launch_conv(dtype, 3, 4, C, C, 0, CO, EPI_NHWC, a, st);
-    }
-    // weight gradients: one launch per pixel-shuffle phase z over the nseg (X, dY) pairs, X = the layer's input (N,H,W,C), dY = phase z
-    // of the gradient into it (a contiguous plane when dy_planes, else every second pixel of every second row of the 2H x 2W image)
-    int ps_wgrads(const void* const* x, const void* const* dy, int nseg, bool dy_planes, int N, int H, int W, float* gw, float* gb, int accumulate) const {
-        for (int z = 0; z < 4; ++z) {
-            WgradArgs a = wg_base(N, H, W, C, C);
-            a.nseg = nseg;
-            for (int i = 0; i < nseg; ++i) {
-                a.x[i] = x[i];
-                a.dy[i] = dy_planes ? (const char*)dy[i] + (size_t)z * plane_elems(N, 2 * H, 2 * W) * es : dy[i];      // plane z: N x H x W, contiguous
-            }
-            if (!dy_planes) { a.dy_step = 2; a.dy_oy = z >> 1; a.dy_ox = z & 1; a.Hy = 2 * H; a.Wy = 2 * W; a.dy_nstride = pm_image_elems(2 * H, 2 * W, C); }
-            CK(wgrad(a, {3, C, false, C, false}, {C, C, gw, C, 0, 4, z, gb, accumulate}));
-        }
-        return VSR_OK;
-    }
-
-    // ---- the ResidualBlock stem (conv.py:97): conv3x3 on cat([lr(3), feat(C)]) (cat) or on lr alone ----
-    // cat: source 0 = feat = input channels 3..C+2, source 1 = LR = 0..2 (basicvsr.py:56,71): two weight sets, feat's first
-    int pack_stem(const float* w, void* dst, bool cat) const {
-        const int I_total = cat ? C + 3 : 3;
-        if (cat) CK(pack(w, dst, 9, CO, C, C, C, I_total, 3, 1, 0, 0));
-        return pack(w, (char*)dst + (cat ? (size_t)9 * CO * C * es : 0), 9, CO, 16, C, 3, I_total, 0, 1, 0, 0);
-    }
-    // data-gradient weights: towards feat (conv(3, ...) runs them), towards the 3 LR channels (conv_planar3)
-    int pack_stem_dgrad(const float* w, void* dst) const { return pack(w, dst, 9, CO, C, C, C, C + 3, 3, 1, 0, 1); }
-    int pack_stem_dlr(const float* w, void* dst, bool cat) const { return pack(w, dst, 9, 32, C, 3, C, cat ? C + 3 : 3, 0, 1, 0, 1); }
-    // feat: null => zeros (first frame of a direction); lr: planar fp32, lr_nstride floats between images
-    int stem(bool cat, const void* feat, const float* lr, long long lr_nstride, const void* wpack, const float* bias, void* y, int act, float slope,
-             int N, int H, int W) const {
-        ConvArgs a = conv_args(N, H, W, C);
-        a.wpack = wpack; a.bias = bias; a.dst[0] = y; a.act = act; a.leaky_slope = slope;
-        a.src[cat ? 1 : 0] = lr; a.src_nstride[cat ? 1 : 0] = lr_nstride;
-        if (!cat) return vsr_launch_conv(dtype, 3, 1, 16, 16, 1, CO, EPI_NHWC, a, st);
-        a.src[0] = feat;
-        return vsr_launch_conv(dtype, 3, 2, C, 16, 1, CO, EPI_NHWC, a, st);
-    }
-    // a_lr: X = the planar LR frames (+ the bias gradient); a_feat (cat, skipped without segments): X = feat
-    int stem_wgrads(bool cat, WgradArgs& a_lr, WgradArgs& a_feat, float* gw, float* gb, int accumulate) const {
-        const int I_total = cat ? C + 3 : 3;
-        CK(wgrad(a_lr, {3, 16, true, C, false}, {C, 3, gw, I_total, 0, 1, 0, gb, accumulate}));
-        if (cat && a_feat.nseg) CK(wgrad_cc(3, a_feat, gw, I_total, 3, nullptr, accumulate));
-        return VSR_OK;
-    }
-
-    // ---- SPyNet layer j (spynet.py:16-18) ----
-    // mode 0: forward weights; mode 1: data-gradient weights, rows = the conv's input channels (template COUT of the dgrad launch), K = its outputs
-    int pack_spy(int j, const float* w, void* dst, int mode) const {
-        if (mode == 0) return pack(w, dst, 49, SPY_COP[j], SPY_CIP[j], SPY_CO[j], SPY_CI[j], SPY_CI[j], 0, 1, 0, 0);
-        return pack(w, dst, 49, SPY_DROWS[j], SPY_DK[j], SPY_CI[j], SPY_CO[j], SPY_CI[j], 0, 1, 0, 1);
-    }
-    // y: pixel-major with SPY_CD[j] channels (j < 4) or planar fp32 (N,2,H,W) (+ pres) for the last layer
-    int spy_conv(int j, const void* x, const void* wpack, const float* bias, void* y, int act, float slope, const float* pres, int N, int H, int W) const {
-        ConvArgs a = conv_args(N, H, W, SPY_CD[j]);
-        a.src[0] = x; a.src_nstride[0] = pm_image_elems(H, W, SPY_CIP[j]);
-        a.wpack = wpack; a.bias = bias; a.act = act; a.leaky_slope = slope; a.cout_real = SPY_CO[j]; a.dst[0] = y;
-        if (j < NSPY - 1) return vsr_launch_conv(dtype, 7, 1, SPY_CIP[j], SPY_CIP[j], 0, SPY_COP[j], EPI_NHWC, a, st);
-        a.dst_nstride = (long long)2 * H * W; a.pres = pres;
-        return vsr_launch_conv(dtype, 7, 1, 16, 16, 0, 32, EPI_PLANAR, a, st);
-    }
-    // dX_j = dgrad(conv_j)(dY_j) (* ReLU'(aux)); dy: pixel-major with SPY_DK[j] channels
-    int spy_dgrad(int j, const void* dy, const void* wpackd, void* dx, const void* aux, int N, int H, int W) const {
-        const int CI = SPY_CIP[j], DK = SPY_DK[j];
-        ConvArgs a = conv_args(N, H, W, CI);
-        a.src[0] = dy; a.src_nstride[0] = pm_image_elems(H, W, DK);
-        a.wpack = wpackd; a.dst[0] = dx; a.cout_real = j == 0 ? 8 : CI;
-        if (aux) { a.aux[0] = aux; a.mask_mode = MASK_RELU; }
-        return vsr_launch_conv(dtype, 7, 1, DK, DK, 0, SPY_DROWS[j], EPI_NHWC, a, st);
-    }
-    int spy_wgrad(int j, const void* x, const void* dy, int N, int H, int W, float* gw, float* gb, int accumulate) const {
-        const int CI = SPY_CIP[j], DK = SPY_DK[j];
-        // fp32, 64 input channels: two 32-channel halves (the 14x38-pixel fp32 tile of 64 channels exceeds LDS)
-        const int nhalf = (dtype == VSR_F32 && CI == 64) ? 2 : 1;
-        for (int hf = 0; hf < nhalf; ++hf) {
-            WgradArgs a = wg_base(N, H, W, CI, DK);
-            a.x[0] = x; a.dy[0] = dy;
-            const int cx = CI / nhalf;
-            if (nhalf == 2) { a.x_ctotal = CI; a.x_coff = hf * (cx / 8); }
-            const int cin_real = nhalf == 2 ? cx : SPY_CI[j];
-            CK(wgrad(a, {7, cx, false, DK, false}, {SPY_CO[j], cin_real, gw, SPY_CI[j], hf * cx, 1, 0, hf == 0 ? gb : nullptr, accumulate}));
-        }
-        return VSR_OK;
-    }
-
-    // ---- weight gradients: one launch into this stream's slab buffer + its reduction (host.h) ----
-    int wgrad(WgradArgs& a, const WgradShape& s, const WgradDst& d, bool even = true) const { return wgrad_run(st, dtype, slab, a, s, d, even); }
-    // C -> C (3x3 / 1x1) into input channels [i_off, i_off + C) of gw's I_total
-    int wgrad_cc(int ks, WgradArgs& a, float* gw, int I_total, int i_off, float* gb, int accumulate) const {
-        return wgrad(a, {ks, C, false, C, false}, {C, C, gw, I_total, i_off, 1, 0, gb, accumulate});
-    }
-
-    // C -> C (3x3 / 1x1): mode 0 forward, 1 data gradient (flipped, transposed)
-    int pack_cc(int ks, const float* w, void* dst, int mode) const { return pack(w, dst, ks * ks, CO, C, C, C, C, 0, 1, 0, mode); }
-    int pack(const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
-             int o_add, int mode) const {
-        return pack_any(dtype, w, dst, KK, RP, CPd, r_real, c_real, I_total, i_off, o_mul, o_add, mode);
-    }
-    int pack_bias(const float* b, void* dst, int nreal, int o_mul = 1, int o_add = 0) const {
-        return pack_any(VSR_F32, b, dst, 1, nreal, 1, nreal, 1, 1, 0, o_mul, o_add, 0);
-    }
-    int pack_any(int dt, const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int o_mul,
-                 int o_add, int mode) const {
-        if (!batch) return vsr_launch_pack_weights(dt, w, dst, KK, RP, CPd, r_real, c_real, I_total, i_off, o_mul, o_add, mode, st);
-        VsrPackDesc d = {};
-        d.w = w; d.dst = dst; d.total = KK * RP * CPd;
-        d.KK = (short)KK; d.RP = (short)RP; d.CPd = (short)CPd; d.r_real = (short)r_real; d.c_real = (short)c_real;
-        d.I_total = (short)I_total; d.i_off = (short)i_off; d.o_mul = (short)o_mul; d.o_add = (short)o_add;
-        d.mode = (unsigned char)mode; d.dtype = (unsigned char)dt;
-        batch->push_back(d);
-        return VSR_OK;
-    }
-};
-
 // lane 0: the caller's stream, 1: the helper stream (selects the per-stream weight-gradient slab buffer)
 Ctx engine_ctx(const Plan& p, char* ws, hipStream_t st, int lane) {
     return Ctx(ws, st, p.dtype, p.C, p.bwd ? reinterpret_cast<float*>(ws + p.slab[lane]) : nullptr);
@@ -496,55 +228,6 @@ struct PIdx {
     int spy_std() const { return spy_base() + 61; }
     int count() const { return spy_base() + 62; }
 };
-
-// ---- SPyNet (spynet.py:38-93) for P frame pairs ------------------------------------------------
-// frames: planar fp32 (F,3,h,w).  pair_mode 0: BasicVSR pairing over (n,t) (basicvsr.py:32-35);
-// pair_mode 1: frames = [ref_0..ref_{P-1}, supp_0..supp_{P-1}].
-int spynet_pack(const Ctx& c, const SpyPlan& sp, const float* const* params, int base_idx) {
-    for (int l = 0; l < 6; ++l)
-        for (int j = 0; j < NSPY; ++j) {
-            const float* w = params[base_idx + (l * NSPY + j) * 2];
-            const float* b = params[base_idx + (l * NSPY + j) * 2 + 1];
-            CK(c.pack_spy(j, w, c.at(sp.wpack[l][j]), 0));
-            CK(c.pack_bias(b, c.at(sp.bias[l][j]), SPY_CO[j]));
-            if (sp.save) CK(c.pack_spy(j, w, c.at(sp.wpackd[l][j]), 1));
-        }
-    return VSR_OK;
-}
-
-// last_relu: the reference's RealBasicVSR Spynet ends every level in a ReLU (spynet.py:16-18); the canonical SPyNet of
-// vsr/models/VRT/modules/spynet.py:76 does not.  level_out[l] (optional, l = 0..5): the level's flow resized to
-// (h >> (5-l), w >> (5-l)) like VRT's return_levels (VRT/modules/spynet.py:134-141).
-int spynet_run(const Ctx& c, const SpyPlan& sp, const float* frames, const float* mean, const float* std, int n, int t,
-               int pair_mode, float* flows_out, bool last_relu = true, float* const* level_out = nullptr) {
-    const int P = sp.P, F = sp.F, hu = sp.hu, wu = sp.wu;
-    CK(vsr_launch_resize_norm(frames, (float*)c.at(sp.pyr[5]), mean, std, F, sp.h, sp.w, hu, wu, c.st));
-    for (int l = 5; l > 0; --l)
-        CK(vsr_launch_avgpool2(c.fat(sp.pyr[l]), (float*)c.at(sp.pyr[l - 1]), (long long)F * 3, hu >> (5 - l), wu >> (5 - l), c.st));
-    size_t fprev = sp.flow_a, fcur = sp.flow_b;
-    for (int l = 0; l < 6; ++l) {
-        const int hl = hu >> (5 - l), wl = wu >> (5 - l);
-        const size_t fup = sp.save ? sp.sfup[l] : sp.flow_up;
-        const size_t bufs[NSPY + 1] = {sp.save ? sp.sx[l][0] : sp.x16, sp.save ? sp.sx[l][1] : sp.b32a, sp.save ? sp.sx[l][2] : sp.b64,
-                                       sp.save ? sp.sx[l][3] : sp.b32b, sp.save ? sp.sx[l][4] : sp.b16, 0};
-        CK(vsr_launch_spynet_prepare(c.dtype, c.fat(sp.pyr[l]), l == 0 ? nullptr : c.fat(fprev), (float*)c.at(fup), c.at(bufs[0]),
-                                     n, t, P, pair_mode, hl, wl, l == 0, c.st));
-        for (int j = 0; j < NSPY; ++j) {
-            const int act = (j < NSPY - 1 || last_relu) ? ACT_RELU : ACT_NONE;     // RealBasicVSR's Spynet: ReLU after the LAST conv too (spynet.py:16-18)
-            // the last layer: flow = flow_up + residue (spynet.py:65); save: keep the residue, its sign is the last ReLU's mask
-            void* y = j < NSPY - 1 ? c.at(bufs[j + 1]) : c.at(sp.save ? sp.sres[l] : fcur);
-            const float* pres = (j == NSPY - 1 && !sp.save) ? c.fat(fup) : nullptr;
-            CK(c.spy_conv(j, c.at(bufs[j]), c.at(sp.wpack[l][j]), c.fat(sp.bias[l][j]), y, act, 0.f, pres, P, hl, wl));
-            if (j == NSPY - 1 && sp.save)
-                CK(vsr_launch_add_f32(c.fat(fup), c.fat(sp.sres[l]), (float*)c.at(fcur), (long long)P * 2 * hl * wl, c.st));
-        }
-        if (level_out && level_out[l])
-            CK(vsr_launch_flow_out(c.fat(fcur), level_out[l], P, hl, wl, sp.h >> (5 - l), sp.w >> (5 - l), c.st));
-        size_t tmp = fprev; fprev = fcur; fcur = tmp;
-    }
-    if (!flows_out) return VSR_OK;
-    return vsr_launch_flow_out(c.fat(fprev), flows_out, P, hu, wu, sp.h, sp.w, c.st);
-}
 
 int pack_all_collect(const Ctx& c, const Plan& p, const float* const* prm);
 // every weight / bias pack of a forward (~465 tensors) in a handful of multi-tensor launches
@@ -590,7 +273,7 @@ int pack_all_collect(const Ctx& c, const Plan& p, const float* const* prm) {
     CK(c.pack(prm[ix.last2_w()], c.at(p.last2_w), 9, 32, 64, 3, 64, 64, 0, 1, 0, 0));
     if (p.bwd) CK(c.pack(prm[ix.last2_w()], c.at(p.last2_wd), 9, 64, 16, 64, 3, 64, 0, 1, 0, 1));
     CK(c.pack_bias(prm[ix.last2_b()], c.at(p.last2_b), 3));
-    if (p.t > 1) CK(spynet_pack(c, p.spy, prm, ix.spy_base()));
+    if (p.t > 1) CK(vsr::spynet_pack(c, p.spy, prm, ix.spy_base()));
     return VSR_OK;
 }
 
@@ -775,7 +458,7 @@ int forward_impl(const Plan& p, const float* const* prm, const float* lrs, float
     const PIdx ix{p.rb, p.ups};
     const int n = p.n, t = p.t;
     CK(pack_all(c, p, prm));
-    if (t > 1) CK(spynet_run(c, p.spy, lrs, prm[ix.spy_mean()], prm[ix.spy_std()], n, t, 0, (float*)c.at(p.flows)));
+    if (t > 1) CK(vsr::spynet_run(c, p.spy, lrs, prm[ix.spy_mean()], prm[ix.spy_std()], n, t, 0, (float*)c.at(p.flows)));
     {
         Fork f{st, nullptr};
         // (chain launches spin on each other's tiles: two of them side by side could each hold the CUs the other's unstarted
@@ -791,57 +474,6 @@ int forward_impl(const Plan& p, const float* const* prm, const float* lrs, float
 }
 
 // ---- backward ------------------------------------------------------------------------------------
-// Backward of spynet_run for train_flow (spynet.py:38-93): dflows_out = d loss / d flows (P,2,h,w) ->
-// weight / bias gradients of the 6 x 5 convs (g[base_idx ...], OIHW fp32).  The frames are not differentiated.
-// dframes (optional): (F,3,h,w) fp32, ACCUMULATED into: the gradient w.r.t. the input frames (through the pyramid).
-// last_relu = false: the canonical SPyNet (no ReLU behind a level's last conv); dlevel (optional, 6 entries, NULL = none):
-// cotangents of the per-level outputs of spynet_run's level_out (VRT's return_levels); dflows_out may then be NULL.
-int spynet_backward(const Ctx& c, const SpyPlan& sp, const float* dflows_out, int n, int t, int pair_mode, float* const* g,
-                    int base_idx, float* dframes = nullptr, const float* std = nullptr, bool last_relu = true,
-                    const float* const* dlevel = nullptr) {
-    const int P = sp.P, hu = sp.hu, wu = sp.wu;
-    size_t dcur = sp.dfa, dprev = sp.dfb;
-    HIP_CHECK_RET(hipMemsetAsync(c.at(dcur), 0, (size_t)P * 2 * hu * wu * 4, c.st));
-    if (dflows_out) CK(vsr_launch_flow_out_bwd(dflows_out, (float*)c.at(dcur), P, hu, wu, sp.h, sp.w, c.st));
-    if (dframes)
-        for (int l = 0; l < 6; ++l)
-            HIP_CHECK_RET(hipMemsetAsync(c.at(sp.dpyr[l]), 0, (size_t)sp.F * 3 * (hu >> (5 - l)) * (wu >> (5 - l)) * 4, c.st));
-    for (int l = 5; l >= 0; --l) {
-        const int hl = hu >> (5 - l), wl = wu >> (5 - l);
-        if (dlevel && dlevel[l])   // this level's flow was also an output (resized to the frame's own pyramid size): add its cotangent
-            CK(vsr_launch_flow_out_bwd(dlevel[l], (float*)c.at(dcur), P, hl, wl, sp.h >> (5 - l), sp.w >> (5 - l), c.st));
-        // flow_l = flow_up + ReLU(conv5): dY of the last conv, as a 16-channel pixel-major tensor
-        CK(vsr_launch_spynet_dres(c.dtype, c.fat(dcur), last_relu ? c.fat(sp.sres[l]) : nullptr, c.at(sp.dres), P, hl, wl, c.st));
-        size_t dy = sp.dres;
-        for (int j = NSPY - 1; j >= 0; --j) {
-            float* gw = g ? g[base_idx + (l * NSPY + j) * 2] : nullptr;
-            float* gb = g ? g[base_idx + (l * NSPY + j) * 2 + 1] : nullptr;
-            CK(c.spy_wgrad(j, c.at(sp.sx[l][j]), c.at(dy), P, hl, wl, gw, gb, 1));
-            if (j == 0 && l == 0 && !dframes) break;       // level 0's input depends on the frames only
-            // dX_j = dgrad(conv_j)(dY_j) (* ReLU'(X_j) for j > 0: X_j is the previous conv's ReLU output)
-            const size_t dx = (dy == sp.gA) ? sp.gB : sp.gA;
-            CK(c.spy_dgrad(j, c.at(dy), c.at(sp.wpackd[l][j]), c.at(dx), j > 0 ? c.at(sp.sx[l][j]) : nullptr, P, hl, wl));
-            dy = dx;
-        }
-        float* dfr = dframes ? (float*)c.at(sp.dpyr[l]) : nullptr;
-        if (l == 0) {
-            if (dfr) CK(vsr_launch_spynet_prepare_bwd(c.dtype, c.at(dy), nullptr, c.fat(sp.pyr[0]), nullptr, nullptr, dfr, n, t, P, pair_mode, hl, wl, c.st));
-            break;
-        }
-        // x16 = [ref | warp(supp, flow_up) | flow_up], flow_up = 2 * up(flow_{l-1}): everything that reaches flow_{l-1}
-        HIP_CHECK_RET(hipMemsetAsync(c.at(dprev), 0, (size_t)P * 2 * (hl / 2) * (wl / 2) * 4, c.st));
-        CK(vsr_launch_spynet_prepare_bwd(c.dtype, c.at(dy), c.fat(dcur), c.fat(sp.pyr[l]), c.fat(sp.sfup[l]), (float*)c.at(dprev), dfr,
-                                         n, t, P, pair_mode, hl, wl, c.st));
-        const size_t tmp = dcur; dcur = dprev; dprev = tmp;
-    }
-    if (dframes) {   // pyramid adjoint: avg_pool2d from fine to coarse (spynet.py:44-45), then the /32 resize + normalisation
-        for (int l = 1; l < 6; ++l)
-            CK(vsr_launch_avgpool2_bwd_add(c.fat(sp.dpyr[l - 1]), (float*)c.at(sp.dpyr[l]), (long long)sp.F * 3, hu >> (5 - l), wu >> (5 - l), c.st));
-        CK(vsr_launch_resize_norm_bwd(c.fat(sp.dpyr[5]), dframes, std, sp.F, sp.h, sp.w, hu, wu, c.st));
-    }
-    return VSR_OK;
-}
-
 // Weight gradients of PixelShufflePack k (upsample.k, upsampling.py:7) for the frames [f0, f1): one launch per pixel-shuffle phase z,
 // X = the layer's input, dY = phase z of the gradient into it (a contiguous plane when p.unsh, else every second pixel of every second row)
 int recon_ps_wgrads(const Ctx& c, const Plan& p, int k, int f0, int f1, float* const* g) {
@@ -1056,7 +688,7 @@ int backward_impl(const Plan& p, const float* const* prm, float* const* g, const
             }
     }
     if (p.flowgrad && p.t > 1)   // part 3 (and train_flow): through the flows into SPyNet's parameters / image pyramid
-        CK(spynet_backward(c, p.spy, c.fat(p.dflows), p.n, p.t, 0, g, PIdx{p.rb, p.ups}.spy_base(), dlrs, prm[PIdx{p.rb, p.ups}.spy_std()]));
+        CK(vsr::spynet_backward(c, p.spy, c.fat(p.dflows), p.n, p.t, 0, g, PIdx{p.rb, p.ups}.spy_base(), dlrs, prm[PIdx{p.rb, p.ups}.spy_std()]));
     return VSR_OK;
 }
 
@@ -1156,527 +788,6 @@ int vsr_basicvsr_narrow_backward(const VsrBasicVSRDesc* d, const float* const* p
 }
 int vsr_basicvsr_narrow_get_flows(const VsrBasicVSRDesc* d, const void* workspace, float* flow_forward, float* flow_backward, void* stream) {
     return basicvsr_get_flows(d, workspace, flow_forward, flow_backward, stream, true);
-}
-
-// ---- SPyNet alone ---------------------------------------------------------------------------------
-struct SpyAlone { SpyPlan sp; size_t frames = 0, slab = 0, dframes = 0, total = 0; };
-static SpyAlone spy_alone_plan(int N, int h, int w, int dtype, bool save) {
-    SpyAlone s; Bump b;
-    s.frames = b.take((size_t)2 * N * 3 * h * w * 4);
-    s.sp.plan(b, N, 2 * N, h, w, dtype);
-    if (save) {                                  // appended: the forward-only offsets do not move
-        s.sp.plan_save(b, dtype);
-        s.slab = b.take(wgrad_slab_bytes());
-        s.dframes = b.take((size_t)2 * N * 3 * h * w * 4);
-    }
-    s.total = b.off;
-    return s;
-}
-// the stand-alone forward / backward behind the four entries below (each entry checks its own arguments first)
-static int spy_alone_forward(int N, int h, int w, int dtype, const float* const* params, const float* ref, const float* supp, float* flow,
-                             bool last_relu, float* const* level_out, void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
-    if (bad_dtype(dtype)) return VSR_ERR_BADARG;
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, need_backward != 0);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const Ctx c((char*)workspace, st, dtype);
-    const size_t fb = (size_t)N * 3 * h * w * 4;
-    HIP_CHECK_RET(hipMemcpyAsync(c.at(s.frames), ref, fb, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK_RET(hipMemcpyAsync((char*)c.at(s.frames) + fb, supp, fb, hipMemcpyDeviceToDevice, st));
-    CK(spynet_pack(c, s.sp, params, 0));
-    return spynet_run(c, s.sp, c.fat(s.frames), params[60], params[61], N, 2, 1, flow, last_relu, level_out);
-}
-static int spy_alone_backward(int N, int h, int w, int dtype, float* const* grads, const float* dflow, const float* std, bool last_relu,
-                              const float* const* dlevel, float* dref, float* dsupp, void* workspace, size_t workspace_bytes, void* stream) {
-    if (bad_dtype(dtype)) return VSR_ERR_BADARG;
-    if (grads) for (int k = 0; k < 60; k += 2) if (!grads[k] && grads[k + 1]) return VSR_ERR_BADARG;   // a bias gradient comes with its weight's
-    const SpyAlone s = spy_alone_plan(N, h, w, dtype, true);
-    if (workspace_bytes < s.total) return VSR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const Ctx c((char*)workspace, st, dtype, 64, (float*)((char*)workspace + s.slab));
-    const bool want = dref || dsupp;
-    const size_t fb = (size_t)N * 3 * h * w * 4;
-    if (want) HIP_CHECK_RET(hipMemsetAsync(c.at(s.dframes), 0, 2 * fb, st));
-    CK(spynet_backward(c, s.sp, dflow, N, 2, 1, grads, 0, want ? (float*)c.at(s.dframes) : nullptr, std, last_relu, dlevel));
-    if (dref) HIP_CHECK_RET(hipMemcpyAsync(dref, c.at(s.dframes), fb, hipMemcpyDeviceToDevice, st));
-    if (dsupp) HIP_CHECK_RET(hipMemcpyAsync(dsupp, (char*)c.at(s.dframes) + fb, fb, hipMemcpyDeviceToDevice, st));
-    return VSR_OK;
-}
-
-size_t vsr_spynet_workspace_bytes(int N, int h, int w, int dtype, int need_backward) {
-    if (bad_dims(N, h, w)) return 0;
-    return spy_alone_plan(N, h, w, dtype, need_backward != 0).total;
-}
-
-int vsr_spynet_forward(int N, int h, int w, int dtype, const float* const* params, int nparams, const float* ref,
-                       const float* supp, float* flow, void* workspace, size_t workspace_bytes, int need_backward, void* stream) {
-    if (N < 1 || h < 1 || w < 1 || !params || nparams != 62 || !ref || !supp || !flow || !workspace) return VSR_ERR_BADARG;
-    return spy_alone_forward(N, h, w, dtype, params, ref, supp, flow, true, nullptr, workspace, workspace_bytes, need_backward, stream);
-}
-
-/* SPyNet with the options of the reference's OTHER SpyNet classes: last_relu = 0 is the canonical network
- * (vsr/models/VRT/modules/spynet.py:68-157); level_out: HOST array of 6 device pointers (NULL entries = not wanted), level l
- * receives the flow of pyramid level l resized to (h >> (5-l), w >> (5-l)) (its `return_levels`).  Forward only.       */
-int vsr_spynet_forward_ex(int N, int h, int w, int dtype, const float* const* params, int nparams, const float* ref,
-                          const float* supp, int last_relu, float* const* level_out, void* workspace, size_t workspace_bytes,
-                          int need_backward, void* stream) {
-    if (N < 1 || h < 32 || w < 32 || !params || nparams != 62 || !ref || !supp || !level_out || !workspace) return VSR_ERR_BADARG;
-    return spy_alone_forward(N, h, w, dtype, params, ref, supp, nullptr, last_relu != 0, level_out, workspace, workspace_bytes, need_backward, stream);
-}
-
-int vsr_spynet_backward(int N, int h, int w, int dtype, float* const* grads, int nparams, const float* dflow, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    if (N < 1 || h < 1 || w < 1 || !grads || nparams != 62 || !dflow || !workspace) return VSR_ERR_BADARG;
-    return spy_alone_backward(N, h, w, dtype, grads, dflow, nullptr, true, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-/* the same, plus the gradient w.r.t. the two input frames: dref, dsupp (N,3,h,w) fp32 are WRITTEN (either may be NULL).
- * params: the 62 tensors of the forward (std is needed for the normalisation's adjoint); grads may be NULL (frozen net). */
-int vsr_spynet_backward_ex(int N, int h, int w, int dtype, const float* const* params, float* const* grads, int nparams, const float* dflow,
-                           int last_relu, const float* const* dlevel, float* dref, float* dsupp, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-    if (N < 1 || h < 1 || w < 1 || !params || nparams != 62 || !workspace || !params[61]) return VSR_ERR_BADARG;
-    bool any = dflow != nullptr;
-    if (dlevel) for (int l = 0; l < 6; ++l) any = any || dlevel[l];
-    if (!any) return VSR_ERR_BADARG;
-    return spy_alone_backward(N, h, w, dtype, grads, dflow, params[61], last_relu != 0, dlevel, dref, dsupp, workspace, workspace_bytes, stream);
-}
-
-// ---- RealBasicVSR pre-clean stack, forward (realbasicvsr.py:17-30) ------------------------------------
-// x <- x + conv(ResidualBlock(x)), `steps` times, on the F = n*t frames of the clip.
-// params: resblock.conv.0.{weight,bias}, resblock.res_block.{i}.conv{1,2}.{weight,bias} ..., conv.{weight,bias}
-struct CleanPlan {
-    size_t stem_w = 0, stem_b = 0, out_w = 0, out_b = 0, feat = 0, act = 0, xa = 0, xb = 0, total = 0;
-    std::vector<size_t> blk_w, blk_b;
-    // need_backward: data-gradient weights, per-step saved tensors, backward scratch
-    bool save = false;
-    size_t stem_wd = 0, out_wd = 0, slab = 0, dXa = 0, dXb = 0, dA = 0, G0 = 0, dxa = 0, dxb = 0;
-    std::vector<size_t> blk_wd;
-    std::vector<size_t> xs;             // [steps]: planar fp32 input of each step (xs[0] unused: the caller's lr)
-    std::vector<size_t> X, A;           // [steps][blocks+1] / [steps][blocks]
-};
-// C: mid channels (64, or 16 / 32 through vsr_cleaner_narrow_workspace_bytes); CO: packed rows of a C-output weight set
-static CleanPlan clean_plan(int F, int h, int w, int blocks, int dtype, int steps, bool save, int C = 64) {
-    CleanPlan p; Bump b;
-    const int CO = C < 32 ? 32 : C;
-    const size_t es = esize(dtype), w64 = (size_t)9 * CO * C * es;
-    p.stem_w = b.take((size_t)9 * CO * 16 * es); p.stem_b = b.take(C * 4);
-    p.blk_w.resize(2 * blocks); p.blk_b.resize(2 * blocks);
-    for (int k = 0; k < 2 * blocks; ++k) { p.blk_w[k] = b.take(w64); p.blk_b[k] = b.take(C * 4); }
-    p.out_w = b.take((size_t)9 * 32 * C * es); p.out_b = b.take(64 * 4);
-    const size_t a1 = (size_t)F * pm_image_elems(h, w, C) * es;
-    const size_t x1 = (size_t)F * 3 * h * w * 4;
-    p.feat = b.take(a1); p.act = b.take(a1);
-    p.xa = b.take(x1); p.xb = b.take(x1);
-    p.save = save;
-    if (save) {                                   // appended: the forward-only offsets do not move
-        p.stem_wd = b.take((size_t)9 * 32 * C * es); p.out_wd = b.take((size_t)9 * CO * 16 * es);
-        p.blk_wd.resize(2 * blocks);
-        for (int k = 0; k < 2 * blocks; ++k) p.blk_wd[k] = b.take(w64);
-        p.slab = b.take(wgrad_slab_bytes());
-        p.dXa = b.take(a1); p.dXb = b.take(a1); p.dA = b.take(a1); p.G0 = b.take(a1);
-        p.dxa = b.take(x1); p.dxb = b.take(x1);
-        p.xs.assign(steps, 0); p.X.assign((size_t)steps * (blocks + 1), 0); p.A.assign((size_t)steps * blocks, 0);
-        for (int s = 0; s < steps; ++s) {
-            if (s > 0) p.xs[s] = b.take(x1);
-            for (int k = 0; k <= blocks; ++k) p.X[(size_t)s * (blocks + 1) + k] = b.take(a1);
-            for (int k = 0; k < blocks; ++k) p.A[(size_t)s * blocks + k] = b.take(a1);
-        }
-    }
-    p.total = b.off;
-    return p;
-}
-
-size_t vsr_cleaner_workspace_bytes(int F, int h, int w, int blocks, int steps, int dtype, int need_backward) {
-    if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1) return 0;
-    return clean_plan(F, h, w, blocks, dtype, steps, need_backward != 0).total;
-}
-
-size_t vsr_cleaner_narrow_workspace_bytes(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, int need_backward) {
-    if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || (mid_channels != 16 && mid_channels != 32)) return 0;
-    if (dtype != VSR_F32 && dtype != VSR_BF16) return 0;
-    return clean_plan(F, h, w, blocks, dtype, steps, need_backward != 0, mid_channels).total;
-}
-static bool cleaner_width_ok(int mid_channels) { return mid_channels == 64 || mid_channels == 32 || mid_channels == 16; }
-
-int vsr_cleaner_forward(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, const float* const* params,
-                        int nparams, const float* lr, float* lq, void* workspace, size_t workspace_bytes, int need_backward,
-                        void* stream) {
-    if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !params || !lr || !lq || !workspace) return VSR_ERR_BADARG;
-    if (!cleaner_width_ok(mid_channels)) return VSR_ERR_UNSUPPORTED;
-    if (bad_dtype(dtype) || nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
-    const bool save = need_backward != 0;
-    const int C = mid_channels;
-    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, save, C);
-    if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
-    const Ctx c((char*)workspace, (hipStream_t)stream, dtype, C);
-    const int CO = c.CO;
-    CK(c.pack_stem(params[0], c.at(p.stem_w), false));
-    CK(c.pack_bias(params[1], c.at(p.stem_b), C));
-    for (int k = 0; k < 2 * blocks; ++k) {
-        CK(c.pack_cc(3, params[2 + 2 * k], c.at(p.blk_w[k]), 0));
-        CK(c.pack_bias(params[3 + 2 * k], c.at(p.blk_b[k]), C));
-        if (save) CK(c.pack_cc(3, params[2 + 2 * k], c.at(p.blk_wd[k]), 1));
-    }
-    CK(c.pack(params[2 + 4 * blocks], c.at(p.out_w), 9, 32, C, 3, C, C, 0, 1, 0, 0));
-    CK(c.pack_bias(params[3 + 4 * blocks], c.at(p.out_b), 3));
-    if (save) {
-        CK(c.pack_stem_dlr(params[0], c.at(p.stem_wd), false));                            // C -> 3 (planar epilogue)
-        CK(c.pack(params[2 + 4 * blocks], c.at(p.out_wd), 9, CO, 16, C, 3, C, 0, 1, 0, 1));     // 3 (planar source) -> C
-    }
-    const float* xin = lr;
-    for (int s = 0; s < steps; ++s) {
-        float* xout = (s == steps - 1) ? lq : (float*)c.at(save ? p.xs[s + 1] : ((s & 1) ? p.xb : p.xa));
-        auto Xs = [&](int k) { return save ? c.at(p.X[(size_t)s * (blocks + 1) + k]) : c.at(p.feat); };
-        // ResidualBlock stem: conv3x3 3->64 + LeakyReLU(0.1) on the planar frames (conv.py:97)
-        CK(c.stem(false, nullptr, xin, (long long)3 * h * w, c.at(p.stem_w), c.fat(p.stem_b), Xs(0), ACT_LEAKY, 0.f, F, h, w));
-        for (int b = 0; b < blocks; ++b) {
-            void* act = save ? c.at(p.A[(size_t)s * blocks + b]) : c.at(p.act);
-            CK(c.conv(3, Xs(b), c.at(p.blk_w[2 * b]), c.fat(p.blk_b[2 * b]), act, ACT_RELU, nullptr, nullptr, 0, F, h, w));
-            CK(c.conv(3, act, c.at(p.blk_w[2 * b + 1]), c.fat(p.blk_b[2 * b + 1]), Xs(b + 1), ACT_NONE, Xs(b), nullptr, 0, F, h, w));
-        }
-        // x + conv3x3 64->3 (realbasicvsr.py:28-29; a fresh tensor instead of the reference's in-place +=)
-        CK(c.conv_planar3(Xs(blocks), c.at(p.out_w), c.fat(p.out_b), xout, (long long)3 * h * w, xin, F, h, w));
-        xin = xout;
-    }
-    return VSR_OK;
-}
-
-// Backward of the above for the cotangent dlq (F,3,h,w): grads[k] (the 4 + 4*blocks tensors; NULL = not wanted, a bias
-// needs its weight's entry) are ACCUMULATED into; dlr (F,3,h,w, optional) is written.  The parameters are shared by the
-// `steps` iterations, so each iteration adds its weight gradients.
-int vsr_cleaner_backward(int F, int h, int w, int mid_channels, int blocks, int steps, int dtype, float* const* grads, int nparams,
-                         const float* lr, const float* dlq, float* dlr, void* workspace, size_t workspace_bytes, void* stream) {
-    if (F < 1 || h < 1 || w < 1 || blocks < 0 || steps < 1 || !grads || !lr || !dlq || !workspace) return VSR_ERR_BADARG;
-    if (!cleaner_width_ok(mid_channels) || blocks < 1) return VSR_ERR_UNSUPPORTED;      // the stem's LeakyReLU mask is fused into block 0's dgrad
-    if (bad_dtype(dtype) || nparams != 4 + 4 * blocks) return VSR_ERR_BADARG;
-    const int C = mid_channels;
-    const CleanPlan p = clean_plan(F, h, w, blocks, dtype, steps, true, C);
-    if (workspace_bytes < p.total) return VSR_ERR_WORKSPACE;
-    const Ctx c((char*)workspace, (hipStream_t)stream, dtype, C, (float*)((char*)workspace + p.slab));
-    const float* dx = dlq;                                   // gradient w.r.t. x_{s+1}
-    for (int s = steps - 1; s >= 0; --s) {
-        const float* xs = s == 0 ? lr : c.fat(p.xs[s]);
-        auto Xs = [&](int k) { return c.at(p.X[(size_t)s * (blocks + 1) + k]); };
-        auto As = [&](int k) { return c.at(p.A[(size_t)s * blocks + k]); };
-        float* gow = grads[2 + 4 * blocks]; float* gob = grads[3 + 4 * blocks];
-        {   // out conv C->3: X = X_blocks, dY = dx (planar)
-            WgradArgs a = wg_base(F, h, w, C, C);
-            a.x[0] = Xs(blocks); a.dy[0] = dx; a.dy_nstride = (long long)3 * h * w;
-            CK(c.wgrad(a, {3, C, false, 16, true}, {3, C, gow, C, 0, 1, 0, gob, 1}));
-        }
-        size_t dcur = p.dXa, dnext = p.dXb;
-        // d X_blocks = dgrad(out conv)(dx): planar 3 -> C, the stem's launch on the flipped weights
-        CK(c.stem(false, nullptr, dx, (long long)3 * h * w, c.at(p.out_wd), nullptr, c.at(dcur), ACT_NONE, 0.f, F, h, w));
-        for (int b = blocks - 1; b >= 0; --b) {   // x + conv2(relu(conv1(x)))   (conv.py:89-92)
-            CK(c.conv(3, c.at(dcur), c.at(p.blk_wd[2 * b + 1]), nullptr, c.at(p.dA), ACT_NONE, nullptr, As(b), MASK_RELU, F, h, w));
-            {
-                WgradArgs a = wg_base(F, h, w, C, C);
-                a.x[0] = As(b); a.dy[0] = c.at(dcur);
-                CK(c.wgrad_cc(3, a, grads[2 + 2 * (2 * b + 1)], C, 0, grads[3 + 2 * (2 * b + 1)], 1));
-            }
-            void* out = b > 0 ? c.at(dnext) : c.at(p.G0);      // b == 0: also through the stem's LeakyReLU
-            CK(c.conv(3, c.at(p.dA), c.at(p.blk_wd[2 * b]), nullptr, out, ACT_NONE, c.at(dcur), b == 0 ? Xs(0) : nullptr,
-                        b == 0 ? MASK_LEAKY : 0, F, h, w));
-            {
-                WgradArgs a = wg_base(F, h, w, C, C);
-                a.x[0] = Xs(b); a.dy[0] = c.at(p.dA);
-                CK(c.wgrad_cc(3, a, grads[2 + 2 * (2 * b)], C, 0, grads[3 + 2 * (2 * b)], 1));
-            }
-            const size_t tmp = dcur; dcur = dnext; dnext = tmp;
-        }
-        const void* g0 = c.at(p.G0);
-        {   // stem 3->C: X = x_s (planar), dY = G0
-            WgradArgs a = wg_base(F, h, w, C, C);
-            a.x[0] = xs; a.x_nstride = (long long)3 * h * w; a.dy[0] = g0;
-            CK(c.stem_wgrads(false, a, a, grads[0], grads[1], 1));
-        }
-        const bool last = s == 0;
-        if (!last || dlr) {   // d x_s = d x_{s+1} + dgrad(stem)(G0)
-            float* dxs = last ? dlr : (float*)c.at((s & 1) ? p.dxa : p.dxb);
-            CK(c.conv_planar3(g0, c.at(p.stem_wd), nullptr, dxs, (long long)3 * h * w, dx, F, h, w));
-            dx = dxs;
-        }
-    }
-    return VSR_OK;
-}
-
-// ---- per-op entry points -------------------------------------------------------------------------
-static bool layer_width_ok(int c) { return c == 16 || c == 32 || c == 64; }      // the widths of the per-op trunk / stem / shuffle layers
-
-int vsr_flow_warp_fwd(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H, int W, int Cc, void* stream) {
-    return vsr_flow_warp_fwd_ex(dtype, in_pm, flow, out_pm, N, H, W, Cc, 0, stream);
-}
-int vsr_flow_warp_bwd(int dtype, const void* dout_pm, const float* flow, float* dacc, int N, int H, int W, int Cc, void* stream) {
-    return vsr_flow_warp_bwd_ex(dtype, dout_pm, flow, dacc, N, H, W, Cc, 0, stream);
-}
-int vsr_flow_warp_bwd_flow(int dtype, const void* in_pm, const void* dout_pm, const float* flow, float* dflow, int N, int H, int W,
-                           int Cc, void* stream) {
-    return vsr_flow_warp_bwd_flow_ex(dtype, in_pm, dout_pm, flow, dflow, N, H, W, Cc, 0, stream);
-}
-/* padding_mode: 0 = 'zeros' (the propagation warps), 1 = 'border' (the warps inside SPyNet, spynet.py:60) */
-int vsr_flow_warp_fwd_ex(int dtype, const void* in_pm, const float* flow, void* out_pm, int N, int H, int W, int Cc, int padding_mode,
-                         void* stream) {
-    if (bad_dtype(dtype) || !in_pm || !flow || !out_pm || bad_dims(N, H, W) || Cc < 16 || (Cc & 15) || (padding_mode & ~1)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_fwd(dtype, in_pm, flow, out_pm, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream, padding_mode);
-}
-int vsr_flow_warp_bwd_ex(int dtype, const void* dout_pm, const float* flow, float* dacc, int N, int H, int W, int Cc, int padding_mode,
-                         void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !dacc || bad_dims(N, H, W) || Cc < 16 || (Cc & 15) || (padding_mode & ~1)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd(dtype, dout_pm, flow, dacc, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream, padding_mode);
-}
-// Test hook (not in the header): the engine's GATHER form of the 64-channel zeros-padding warp adjoint on its own -- out = T(dtop + adjoint(dout)),
-// near sources gathered, far ones through the 64-bit fixed-point accumulator S (N*H*W*64 long longs, all zero on entry and exit;
-// far_count: one zeroed int).  tests: against the scatter form above, and that a non-finite far contribution stays non-finite.
-extern "C" int vsr_debug_warp_bwd_gather(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
-                                         void* out_pm, int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, 64, (long long)2 * H * W, (hipStream_t)stream);
-}
-// ... the same at Cc = 16, 32 or 64 channels (S: N*H*W*Cc long longs): the narrow engine's propagation warps
-extern "C" int vsr_debug_warp_bwd_gather_c(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
-                                           void* out_pm, int N, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
-}
-int vsr_flow_warp_bwd_flow_ex(int dtype, const void* in_pm, const void* dout_pm, const float* flow, float* dflow, int N, int H, int W,
-                              int Cc, int padding_mode, void* stream) {
-    if (bad_dtype(dtype) || !in_pm || !dout_pm || !flow || !dflow || bad_dims(N, H, W) || Cc < 16 || (Cc & 15) || (padding_mode & ~1)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_flow(dtype, in_pm, dout_pm, flow, dflow, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream, padding_mode);
-}
-int vsr_planar_to_pm(int dtype, const float* in, void* out_pm, int N, int Cin, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !in || !out_pm || bad_dims(N, H, W) || Cin < 1 || Cc < Cin || (Cc & 15)) return VSR_ERR_BADARG;
-    return vsr_launch_planar_to_pm(dtype, in, out_pm, N, Cin, H, W, Cc, (hipStream_t)stream);
-}
-int vsr_pm_to_planar(int dtype, const void* in_pm, float* out, int N, int Cout, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !in_pm || !out || bad_dims(N, H, W) || Cout < 1 || Cc < Cout || (Cc & 15)) return VSR_ERR_BADARG;
-    return vsr_launch_pm_to_planar(dtype, in_pm, out, N, Cout, H, W, Cc, (hipStream_t)stream);
-}
-
-int vsr_conv3x3_c64_fwd(int dtype, const void* x_pm, const float* w, const float* b, void* wpack, void* y_pm, const void* res_pm,
-                        int act, int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !x_pm || !wpack || !y_pm || bad_dims(N, H, W) || act < ACT_NONE || act > ACT_LEAKY) return VSR_ERR_BADARG;
-    const Ctx c(nullptr, (hipStream_t)stream, dtype);
-    if (w) CK(c.pack_cc(3, w, wpack, 0));   // w == NULL: wpack already packed
-    return c.conv(3, x_pm, wpack, b, y_pm, act, res_pm, nullptr, 0, N, H, W);
-}
-
-size_t vsr_conv3x3_c64_chain_sync_bytes(int nlayers, int N, int H, int W) {
-    if (nlayers < 1 || nlayers > VSR_CHAIN_MAX_LAYERS || bad_dims(N, H, W)) return 0;
-    return vsr_chain_sync_bytes(nlayers, N, H, W);
-}
-
-int vsr_conv3x3_c64_chain_fwd(const void* images, const void* wpack, const float* bias, int nlayers, int N, int H, int W, void* sync,
-                              void* stream) {
-    if (!images || !wpack || !bias || !sync || nlayers < 1 || nlayers > VSR_CHAIN_MAX_LAYERS || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    const size_t img = (size_t)N * pm_image_elems(H, W, C) * 2, wset = (size_t)9 * C * C * 2;
-    // the kernel addresses every operand as a 32-bit offset (x 256 B) from one base
-    uintptr_t lo = (uintptr_t)images;
-    if ((uintptr_t)wpack < lo) lo = (uintptr_t)wpack;
-    if ((uintptr_t)bias < lo) lo = (uintptr_t)bias;
-    lo &= ~(uintptr_t)255;
-    auto off = [&](const void* p, size_t add, unsigned* out) {
-        const uintptr_t d = (uintptr_t)p + add - lo;
-        if ((d & 255) || (d >> 8) >= 0xffffffffull) return false;
-        *out = (unsigned)(d >> 8);
-        return true;
-    };
-    ChainArgs a = {};
-    a.base = (char*)lo; a.sync = (unsigned*)sync; a.N = N; a.H = H; a.W = W; a.nlayers = nlayers;
-    for (int l = 0; l < nlayers; ++l) {
-        ChainLayer& L = a.layer[l];
-        L = {0, 0, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, (l & 1) ? CHAIN_SKIP : CHAIN_RELU};
-        bool ok = off(images, (size_t)l * img, &L.src) && off(images, (size_t)(l + 1) * img, &L.dst) && off(wpack, (size_t)l * wset, &L.w) &&
-                  off(bias, (size_t)l * C * 4, &L.bias);
-        if (l & 1) ok = ok && off(images, (size_t)(l - 1) * img, &L.res);
-        if (!ok) return VSR_ERR_UNSUPPORTED;
-    }
-    return vsr_launch_conv3x3_chain(a, vsr_num_cus(), (hipStream_t)stream);
-}
-
-int vsr_conv3x3_c64_dgrad(int dtype, const void* dy_pm, const float* w, void* wpack, void* dx_pm, const void* res_pm,
-                          const void* aux_pm, int mask_mode, int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !dy_pm || !w || !wpack || !dx_pm || bad_dims(N, H, W) || mask_mode < MASK_NONE || mask_mode > MASK_LEAKY ||
-        (mask_mode != MASK_NONE && !aux_pm))
-        return VSR_ERR_BADARG;
-    const Ctx c(nullptr, (hipStream_t)stream, dtype);
-    CK(c.pack_cc(3, w, wpack, 1));
-    return c.conv(3, dy_pm, wpack, nullptr, dx_pm, ACT_NONE, res_pm, aux_pm, mask_mode, N, H, W);
-}
-
-/* Backward of ONE conv layer of vsr_conv_layer_fwd (same shapes, same argument meaning): the reference's building blocks are ordinary
- * autograd modules (core/modules/conv.py:15-22,94-103, upsampling.py:4-12, spynet.py:13-21), so each layer needs its data gradient,
- * weight gradient and bias gradient on its own.  Every piece is a kernel the engines already run:
- *   dyM = dy * act'(y)           (mask_pm / spynet_dres; act'(y) from the layer's stored OUTPUT y: ReLU / LeakyReLU keep the sign)
- *   dx  = conv(dyM, flipped W)   (the forward kernels on weights packed with mode 1; pixel-shuffle: four phase launches)
- *   dlr = the stems' 3 planar LR channels (64 -> 3 planar kernel)
- *   gw, gb = wgrad(x, dyM)       (producer/consumer kernel for 3x3 64->64, generic kernel otherwise; reduced in a fixed order)
- * x_pm / lr_planar / y_* as given to / returned by the forward; dy_* has y's layout.  dx_pm, dlr_planar, gw, gb may be NULL (not
- * needed); gw / gb are OVERWRITTEN.  scratch: vsr_conv_layer_bwd_scratch_bytes(...) bytes.                                         */
-size_t vsr_conv_layer_bwd_scratch_bytes(int dtype, int N, int H, int W, int pixel_shuffle) {
-    if (bad_dtype(dtype) || bad_dims(N, H, W)) return 0;
-    const size_t es = esize(dtype);
-    const int s = pixel_shuffle ? 2 : 1;
-    return (size_t)49 * 64 * 64 * 4 * es + (size_t)N * pm_image_elems(s * H, s * W, C) * es + wgrad_slab_bytes() + 1024;
-}
-
-int vsr_conv_layer_bwd(int dtype, int ks, const void* x_pm, int cin_pm, const float* lr_planar, const float* w, int cin_real, int cout_real,
-                       const void* y_pm, const float* y_planar, const void* dy_pm, const float* dy_planar, int cd, int act, float slope,
-                       int pixel_shuffle, void* dx_pm, float* dlr_planar, float* gw, float* gb, void* scratch, size_t scratch_bytes,
-                       int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !w || !scratch || bad_dims(N, H, W) || (!x_pm && !lr_planar) || (!dy_pm && !dy_planar) || act < ACT_NONE || act > ACT_LEAKY)
-        return VSR_ERR_BADARG;
-    if (act != ACT_NONE && !(dy_pm ? y_pm != nullptr : y_planar != nullptr)) return VSR_ERR_BADARG;     // the mask needs the layer's output
-    if (scratch_bytes < vsr_conv_layer_bwd_scratch_bytes(dtype, N, H, W, pixel_shuffle)) return VSR_ERR_WORKSPACE;
-    if (pixel_shuffle && !layer_width_ok(cin_pm)) return VSR_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t es = esize(dtype);
-    char* wp = (char*)scratch;
-    char* dym = wp + (size_t)49 * 64 * 64 * 4 * es;
-    const int sps = pixel_shuffle ? 2 : 1;
-    float* slab = reinterpret_cast<float*>(dym + (((size_t)N * pm_image_elems(sps * H, sps * W, C) * es + 255) & ~(size_t)255));
-    const float mslope = act == ACT_LEAKY ? vsr_slope(slope) : 0.f;
-
-    if (!dy_pm) {   // planar output: the 16 -> 2 SPyNet layer.  dyM as a 16-channel pixel-major tensor
-        if (ks != 7 || cout_real != 2 || cin_pm != 16 || cin_real != 16 || !x_pm || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
-        if (act == ACT_RELU) CK(vsr_launch_spynet_dres(dtype, dy_planar, y_planar, dym, N, H, W, st));
-        else if (act == ACT_NONE) CK(vsr_launch_planar_to_pm(dtype, dy_planar, dym, N, 2, H, W, 16, st));
-        else return VSR_ERR_UNSUPPORTED;
-    } else if (act != ACT_NONE) {
-        const int cdy = pixel_shuffle ? cin_pm : cd;
-        CK(vsr_launch_mask_pm(dtype, dy_pm, y_pm, dym, mslope, (long long)N * pm_image_elems(sps * H, sps * W, cdy), st));
-    }
-    const void* dyM = (!dy_pm || act != ACT_NONE) ? (const void*)dym : dy_pm;
-
-    // (gw / gb are overwritten: every reduction below writes its own part of them)
-    if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone  (conv.py:97), C = 16, 32 or 64
-        const int C = cout_real;
-        if (ks != 3 || !layer_width_ok(C) || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
-        const bool cat = x_pm != nullptr;
-        if ((cat && (cin_pm != C || cin_real != C + 3)) || (!cat && cin_real != 3)) return VSR_ERR_UNSUPPORTED;
-        const Ctx c(nullptr, st, dtype, C, slab);
-        if (cat && dx_pm) {
-            CK(c.pack_stem_dgrad(w, wp));
-            CK(c.conv(3, dyM, wp, nullptr, dx_pm, ACT_NONE, nullptr, nullptr, 0, N, H, W));
-        }
-        if (dlr_planar) {
-            CK(c.pack_stem_dlr(w, wp, cat));
-            CK(c.conv_planar3(dyM, wp, nullptr, dlr_planar, (long long)3 * H * W, nullptr, N, H, W));
-        }
-        if (gw) {
-            WgradArgs a = wg_base(N, H, W, C, C), af = a;
-            a.x[0] = lr_planar; a.x_nstride = (long long)3 * H * W; a.dy[0] = dyM;
-            af.x[0] = x_pm; af.dy[0] = dyM;
-            CK(c.stem_wgrads(cat, a, af, gw, gb, 0));
-        }
-        return VSR_OK;
-    }
-    if (ks == 3 || ks == 1) {
-        const int C = cin_pm;
-        if (!layer_width_ok(C) || cin_real != C || !x_pm) return VSR_ERR_UNSUPPORTED;
-        const Ctx c(nullptr, st, dtype, C, slab);
-        if (pixel_shuffle) {                               // conv3x3 C -> 4C + PixelShuffle(2)  (upsampling.py:10-12)
-            if (ks != 3 || cout_real != 4 * C || cd != C || act != ACT_NONE) return VSR_ERR_UNSUPPORTED;
-            if (dx_pm) {
-                CK(c.pack_ps(w, wp, 1));
-                CK(c.conv_ps_dgrad(dyM, wp, dx_pm, nullptr, 0, N, H, W));
-            }
-            if (gw) CK(c.ps_wgrads(&x_pm, &dyM, 1, false, N, H, W, gw, gb, 0));
-            return VSR_OK;
-        }
-        if (cout_real != C || cd != C) return VSR_ERR_UNSUPPORTED;
-        if (dx_pm) {
-            CK(c.pack_cc(ks, w, wp, 1));
-            CK(c.conv(ks, dyM, wp, nullptr, dx_pm, ACT_NONE, nullptr, nullptr, 0, N, H, W));
-        }
-        if (gw) {
-            WgradArgs a = wg_base(N, H, W, C, C);
-            a.x[0] = x_pm; a.dy[0] = dyM;
-            CK(c.wgrad_cc(ks, a, gw, C, 0, gb, 0));
-        }
-        return VSR_OK;
-    }
-    if (ks != 7 || pixel_shuffle || !x_pm) return VSR_ERR_UNSUPPORTED;
-    for (int j = 0; j < NSPY; ++j) {                       // the SPyNet layer shapes (spynet.py:16-18), as spynet_backward runs them
-        if (cin_pm != SPY_CIP[j] || cout_real != SPY_CO[j] || cin_real != SPY_CI[j]) continue;
-        if (j < NSPY - 1 && cd != SPY_CD[j]) return VSR_ERR_BADARG;
-        const Ctx c(nullptr, st, dtype, 64, slab);
-        if (gw) CK(c.spy_wgrad(j, x_pm, dyM, N, H, W, gw, gb, 0));
-        if (dx_pm) {
-            CK(c.pack_spy(j, w, wp, 1));
-            CK(c.spy_dgrad(j, dyM, wp, dx_pm, nullptr, N, H, W));
-        }
-        return VSR_OK;
-    }
-    return VSR_ERR_UNSUPPORTED;
-}
-
-/* One convolution layer on blocked pixel-major tensors, forward only: the building blocks the reference's modules expose
- * on their own (ConvReLU core/modules/conv.py:15-22, SpynetModule spynet.py:13-21, PixelShufflePack upsampling.py:4-12,
- * the stem of ResidualBlock conv.py:97).  w: fp32 OIHW (cout_real, cin_real [+3 for lr_planar], ks, ks); b: cout_real or NULL.
- *   ks 3 or 1: x_pm has 64 channels, 64 outputs (pixel_shuffle: 256 outputs written as (N,2H,2W,64), upsampling.py:10-12);
- *   ks 7: (cin_pm, cout) in {(16,32), (32,64), (64,32), (32,16), (16,2 -> y_planar)} (the SPyNet layers);
- *   lr_planar (N,3,H,W) fp32, ks 3: the conv reads cat([lr, x]) (x_pm may be NULL = lr only): the trunk / pre-clean stems.
- * y_pm has cd channels per pixel (16 / 32 / 64); y_planar (N,cout_real,H,W) fp32 instead when cout_real <= 4.
- * wpack: scratch of 49 * 64 * 64 * 4 elements of `dtype` (packed weights of this call).                               */
-int vsr_conv_layer_fwd(int dtype, int ks, const void* x_pm, int cin_pm, const float* lr_planar, const float* w, const float* b,
-                       int cin_real, int cout_real, void* wpack, void* y_pm, int cd, float* y_planar, int act, float slope,
-                       int pixel_shuffle, int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !w || !wpack || bad_dims(N, H, W) || (!x_pm && !lr_planar) || (!y_pm && !y_planar) || act < ACT_NONE || act > ACT_LEAKY)
-        return VSR_ERR_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    char* wp = (char*)wpack;
-    // (the kernels read the bias as fp32 from device memory: the caller's tensor is used as is -- cout_real values, padded reads are masked by cout_real)
-    if (lr_planar) {                                       // stems: cat([lr(3), feat(C)]) or lr alone, C = 16, 32 or 64
-        const int C = cout_real;
-        if (ks != 3 || !layer_width_ok(C) || !y_pm || cd != C || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
-        const bool cat = x_pm != nullptr;
-        if (cat ? (cin_pm != C || cin_real != C + 3) : cin_real != 3) return VSR_ERR_UNSUPPORTED;
-        const Ctx c(nullptr, st, dtype, C);
-        CK(c.pack_stem(w, wp, cat));
-        return c.stem(cat, x_pm, lr_planar, (long long)3 * H * W, wp, b, y_pm, act, slope, N, H, W);
-    }
-    if (ks == 3 || ks == 1) {
-        const int C = cin_pm;
-        if (!layer_width_ok(C) || cin_real != C) return VSR_ERR_UNSUPPORTED;
-        const Ctx c(nullptr, st, dtype, C);
-        if (pixel_shuffle) {
-            if (ks != 3 || cout_real != 4 * C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-            CK(c.pack_ps(w, wp, 0));
-            float* b4 = reinterpret_cast<float*>(wp + (size_t)4 * 9 * c.CO * C * c.es);
-            if (b) CK(c.pack_ps_bias(b, b4));
-            return c.conv_ps(x_pm, wp, b ? b4 : nullptr, y_pm, N, H, W, act, slope);
-        }
-        if (cout_real != C || !y_pm || cd != C) return VSR_ERR_UNSUPPORTED;
-        CK(c.pack_cc(ks, w, wp, 0));
-        return c.conv(ks, x_pm, wp, b, y_pm, act, nullptr, nullptr, 0, N, H, W, nullptr, nullptr, false, slope);
-    }
-    if (ks != 7 || pixel_shuffle) return VSR_ERR_UNSUPPORTED;
-    for (int j = 0; j < NSPY; ++j) {
-        if (cin_pm != SPY_CIP[j] || cout_real != SPY_CO[j] || cin_real != SPY_CI[j]) continue;
-        const Ctx c(nullptr, st, dtype);
-        CK(c.pack_spy(j, w, wp, 0));
-        if (j < NSPY - 1 ? (!y_pm || cd != SPY_CD[j]) : !y_planar) return VSR_ERR_BADARG;
-        return c.spy_conv(j, x_pm, wp, b, j < NSPY - 1 ? y_pm : (void*)y_planar, act, slope, nullptr, N, H, W);
-    }
-    return VSR_ERR_UNSUPPORTED;
-}
-
-size_t vsr_conv3x3_c64_wgrad_slab_floats(void) { return wgrad_slab_floats(); }
-
-int vsr_conv3x3_c64_wgrad(int dtype, const void* x_pm, const void* dy_pm, float* gw, float* gb, float* slab, int N, int H, int W,
-                          void* stream) {
-    if (bad_dtype(dtype) || !x_pm || !dy_pm || !gw || !slab || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    const Ctx c(nullptr, (hipStream_t)stream, dtype, 64, slab);
-    WgradArgs a = wg_base(N, H, W);
-    a.x[0] = x_pm; a.dy[0] = dy_pm;
-    return c.wgrad(a, {3, 64, false, 64, false}, {C, C, gw, C, 0, 1, 0, gb, 0}, false);      // an odd tile count stays odd: wgrad_run()
-}
-
-size_t vsr_charbonnier_scratch_floats(void) { return (size_t)vsr_charbonnier_scratch_floats_impl(); }
-int vsr_charbonnier_fwd_bwd(const float* sr, const float* hr, float* dsr, float* loss, float* scratch, long long numel, float eps, void* stream) {
-    if (!sr || !hr || !dsr || !loss || !scratch || numel < 1) return VSR_ERR_BADARG;
-    return vsr_launch_charbonnier_grad(sr, hr, dsr, loss, scratch, numel, eps, (hipStream_t)stream);
 }
 
 }  // extern "C"

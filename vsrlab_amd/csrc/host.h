@@ -1,5 +1,6 @@
-// Host-side launch layer shared by the engines (engine.hip, disc_engine.hip, perceptual_engine.hip): arena bump allocator, argument
-// checks, the ConvArgs / WgradArgs initialisers and the weight-gradient "launch + reduce" recipe.  No kernel lives here.
+// Host-side launch layer shared by the engines (engine.hip, spynet_engine.hip, cleaner_engine.hip, disc_engine.hip,
+// perceptual_engine.hip) and the per-op entries (layer_ops.hip): arena bump allocator, argument checks, the ConvArgs / WgradArgs
+// initialisers and the weight-gradient "launch + reduce" recipe.  No kernel lives here.  recipes.h builds the BasicVSR side's Ctx on it.
 #pragma once
 #include "kernels.h"
 #include "../../include/vsrlab_hip.h"

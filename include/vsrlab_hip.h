@@ -331,7 +331,9 @@ int vsr_perceptual_loss(const VsrPerceptualDesc* d, const float* const* params, 
  * (B, N, 3, heads, head_dim) contiguous in `dtype`; queries are tokens [q0, q0+Nq), keys / values tokens [k0, k0+Nk)
  * (self attention: both all N tokens; mutual attention of a 2-frame window: the two halves, :128-134), and the result
  * goes to rows [o0, o0+Nq), channels [c_off, c_off + heads*head_dim) of out (B, N, Cout) -- where the reference's torch.cat
- * (:131-134) would put it.  head_dim <= 32; Nq, Nk multiples of 32, <= 384.
+ * (:131-134) would put it.  head_dim <= 32 and EVEN; Nq, Nk multiples of 32, <= 384.  c_off and Cout are multiples of 4
+ * when head_dim is (vector loads / stores of a head's slice of a row), else of 2; every pointer is 16-byte aligned; a dense
+ * mask has Nm % 4 == 0.  Anything else is VSR_ERR_UNSUPPORTED (shape) or VSR_ERR_BADARG (pointer, range), before any launch.
  * bias: dense fp32 (heads, Nq, Nk) or NULL (vsr_rpb_gather builds it from relative_position_bias_table, :146-148);
  * mask: fp32 (nW, Nm, Nm) from compute_mask (:61-77) or NULL -- its top-left Nq x Nk block is used, as the reference does.  */
 typedef struct VsrAttnDesc {

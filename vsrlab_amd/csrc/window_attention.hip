@@ -14,6 +14,7 @@
 // The backward is the usual two passes: query-stationary (delta, dQ, bias gradient) and key-stationary (dK, dV).
 // T = bf16 (v_mfma_f32_16x16x32_bf16) or fp32 (8 x v_mfma_f32_16x16x4_f32 per step: the same fragment layout, exact fp32).
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include "kernels.h"
 #include "../../include/vsrlab_hip.h"
@@ -59,6 +60,7 @@ struct AttnArgs {
     int B, N, nH, hd;
     int q0, k0, o0;             // first query token, first key/value token, first output token row
     int Nq, Nk;
+    int qc;                     // bwd pass 2: queries staged per chunk (divides Nq)
     int Cout, c_off;            // output row length and first channel of this call's heads
     float scale;
 };
@@ -318,12 +320,15 @@ __global__ __launch_bounds__(MAXW * 64) void attn_bwd_q_kernel(const AttnArgs a)
 }
 
 // ============================ backward pass 2: key-stationary (dK, dV) ============================
-constexpr int QC = 128;                      // queries staged in LDS at a time (4 x QC x HP elements: 64 KiB in fp32)
+constexpr int QC = 128;                      // most queries staged in LDS at a time (4 x QC x HP elements: 64 KiB in fp32)
+// Nq <= QC: one chunk.  Above it the chunk must divide Nq: 128, or 96 for the 192 queries of a (3,8,8) window and of the
+// mutual attention of a (6,8,8) one (which `Nq % 128` used to refuse: those windows had a forward and no backward).
+inline int kv_chunk(int Nq) { return Nq <= QC ? Nq : (Nq % QC == 0 ? QC : (Nq % 96 == 0 ? 96 : QC)); }
 template <typename T>
 __global__ __launch_bounds__(MAXW * 64) void attn_bwd_kv_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename AT<T>::frag_t frag_t;
-    const int qc = a.Nq < QC ? a.Nq : QC;
+    const int qc = a.qc;
     T* lds_q = reinterpret_cast<T*>(smem);                  // [qc][HP]   (q * scale)
     T* lds_do = lds_q + qc * HP;                            // [qc][HP]
     const int qts = tstride(qc);
@@ -843,6 +848,9 @@ int launch_attn(K kern, VsrDevOnce& once, const AttnArgs& a, int blocks_x, int w
     return VSR_OK;
 }
 
+// every tensor is read / written with up to 16-byte vector accesses relative to its base
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
 int check_args(const VsrAttnDesc* d, const void* qkv) {
     if (!d || !qkv) return VSR_ERR_BADARG;
     if (d->dtype != VSR_F32 && d->dtype != VSR_BF16) return VSR_ERR_BADARG;
@@ -852,6 +860,14 @@ int check_args(const VsrAttnDesc* d, const void* qkv) {
     if (d->q0 < 0 || d->k0 < 0 || d->o0 < 0 || d->q0 + d->Nq > d->N || d->k0 + d->Nk > d->N || d->o0 + d->Nq > d->N) return VSR_ERR_BADARG;
     if (d->c_off < 0 || d->c_off + d->heads * d->head_dim > d->Cout) return VSR_ERR_BADARG;
     if (d->B > 65535 || d->heads > 65535) return VSR_ERR_UNSUPPORTED;
+    // Stager::load moves element PAIRS under `c < hd`: for an odd head_dim the last pair would take the first element of the
+    // next head (past the tensor for the last one), and a head would start on an odd element.  No VRT configuration has one.
+    if (d->head_dim & 1) return VSR_ERR_UNSUPPORTED;
+    // a head's slice of an out / dout row is moved as pairs (Stager) or, for head_dim % 4 == 0, as 4-element vectors
+    // (load_hd8 / store_hd4): the row length and the first channel must keep those whole and aligned
+    const int al = (d->head_dim & 3) ? 2 : 4;
+    if (d->c_off % al || d->Cout % al) return VSR_ERR_UNSUPPORTED;
+    if (misaligned(qkv)) return VSR_ERR_BADARG;
     return VSR_OK;
 }
 
@@ -869,10 +885,12 @@ AttnArgs make_args(const VsrAttnDesc* d) {
 static int set_mask(const VsrAttnDesc* d, const float* mask, AttnArgs& a) {
     a.mask = nullptr; a.mask_bits = nullptr;
     if (!mask) return VSR_OK;
+    if (d->Nm < d->Nq || d->Nm < d->Nk || misaligned(mask)) return VSR_ERR_BADARG;     // the top-left Nq x Nk block of (nW, Nm, Nm)
     if (d->mask_packed) {
         if (!(d->Nq == d->Nk && (d->Nk == 128 || d->Nk == 64)) || (d->Nm & 31)) return VSR_ERR_UNSUPPORTED;
         a.mask_bits = reinterpret_cast<const unsigned*>(mask);
     } else {
+        if (d->Nm & 3) return VSR_ERR_UNSUPPORTED;          // dense rows are read as float4 from columns 4 q + 16 t
         a.mask = mask;
     }
     return VSR_OK;
@@ -907,7 +925,7 @@ int vsr_rpb_scatter(const float* ddense, const long long* index, int idx_stride,
 int vsr_window_attention_fwd(const VsrAttnDesc* d, const void* qkv, const float* bias, const float* mask, void* out, float* lse, void* stream) {
     int rc = check_args(d, qkv);
     if (rc != VSR_OK) return rc;
-    if (!out) return VSR_ERR_BADARG;
+    if (!out || misaligned(out) || misaligned(bias)) return VSR_ERR_BADARG;
     AttnArgs a = make_args(d);
     a.qkv = qkv; a.out = out; a.lse = lse; a.bias = bias;
     rc = set_mask(d, mask, a);
@@ -943,6 +961,7 @@ int vsr_window_attention_bwd(const VsrAttnDesc* d, const void* qkv, const float*
     int rc = check_args(d, qkv);
     if (rc != VSR_OK) return rc;
     if (!dout || !lse || !delta || !dqkv) return VSR_ERR_BADARG;
+    if (misaligned(dout) || misaligned(dqkv) || misaligned(bias) || misaligned(dbias)) return VSR_ERR_BADARG;
     AttnArgs a = make_args(d);
     a.qkv = qkv; a.dout = dout; a.dqkv = dqkv; a.lse = const_cast<float*>(lse); a.delta = delta; a.bias = bias; a.dbias = dbias;
     rc = set_mask(d, mask, a);
@@ -952,8 +971,9 @@ int vsr_window_attention_bwd(const VsrAttnDesc* d, const void* qkv, const float*
     static VsrDevOnce o2, o4;
     const size_t lds1 = ((size_t)2 * d->Nk * HP + (size_t)HP * (d->Nk + 8)) * es;
     const int wq = d->Nq / WQ < MAXW ? d->Nq / WQ : MAXW, wk = d->Nk / WQ < MAXW ? d->Nk / WQ : MAXW;
-    const int qc = d->Nq < QC ? d->Nq : QC;
+    const int qc = kv_chunk(d->Nq);
     if (d->Nq % qc != 0) return VSR_ERR_UNSUPPORTED;
+    a.qc = qc;
     const size_t lds2 = ((size_t)2 * qc * HP + (size_t)2 * HP * (qc + 8)) * es + (size_t)2 * qc * 4;
     if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return VSR_ERR_UNSUPPORTED;
     if (d->Nq == d->Nk && (d->Nk == 128 || d->Nk == 64)) {

@@ -1107,8 +1107,9 @@ def window_attention_core(qkv_self: torch.Tensor, qkv_mut: Optional[torch.Tensor
     B, N, C3 = qkv_self.shape
     if C3 % (3 * heads) != 0:
         raise ValueError("qkv width must be 3 * heads * head_dim")
-    if (C3 // 3 // heads) > 32 or N % 32 != 0 or N > 384 or (qkv_mut is not None and N % 64 != 0):
-        raise NotImplementedError("HIP window attention: head_dim <= 32 and windows of 64..384 tokens (VRT's (2,8,8) / (6,8,8))")
+    hd = C3 // 3 // heads
+    if hd > 32 or hd % 2 != 0 or N % 32 != 0 or N > 384 or (qkv_mut is not None and N % 64 != 0):
+        raise NotImplementedError("HIP window attention: even head_dim <= 32 and windows of 64..384 tokens (VRT's (2,8,8) / (6,8,8))")
     return _WindowAttentionFn.apply(qkv_self, qkv_mut, table, index[:N, :N], mask, heads, scale, resolve_dtype(compute_dtype))
 
 

@@ -112,6 +112,11 @@ struct WgradArgs {
 };
 
 static inline __host__ __device__ int cdiv(int a, int b) { return (a + b - 1) / b; }
+// 1-D launch grid of a grid-stride kernel: one thread per item up to 4,096 workgroups (16 per CU), never empty
+static inline int grid_for(long long total, int block = 256) {
+    long long g = (total + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
+}
 
 // ---- the internal "pixel-major" layout, blocked by 32 pixels ---------------------------------------
 //   [N][H][WS = ceil(W/32)][C/8 chunks][32 pixels][8 channels]

@@ -19,7 +19,7 @@
 // activation-gradient mask, pixel-shuffle placement, or planar fp32 store with residual /
 // bilinear x4 skip.
 #include <cstdlib>
-#include "common.h"
+#include "elt.h"
 
 namespace {
 
@@ -32,31 +32,21 @@ constexpr int NTHREADS = 256;
 
 // 8-channel chunks in registers are NATIVE vectors: arrays of HIP's uint4 class (the weight-slab prefetch registers) were
 // not promoted to registers by hipcc and went through scratch memory in every instantiation of this kernel (r03: 469 scratch
-// instructions in this file).
+// instructions in this file).  So this file has a chunk_t of its own; the rest of the element layer is elt.h's.
 typedef __attribute__((ext_vector_type(4))) unsigned cu32x4_t;
 typedef __attribute__((ext_vector_type(8))) unsigned cu32x8_t;
-template <typename T> struct Elt;
-template <> struct Elt<bf16_t> {
-    static constexpr int CHB = 16;                 // bytes per 8-channel chunk
-    typedef bf16x8_t frag_t;
-    typedef cu32x4_t chunk_t;
-};
-struct f32x8_t { float v[8]; };
-typedef cu32x8_t chunk32_t;
-template <> struct Elt<float> {
-    static constexpr int CHB = 32;
-    typedef f32x8_t frag_t;
-    typedef chunk32_t chunk_t;
-};
-
-__device__ __forceinline__ void mma(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+template <typename T> struct RegChunk;
+template <> struct RegChunk<bf16_t> { typedef cu32x4_t chunk_t; };
+template <> struct RegChunk<float> { typedef cu32x8_t chunk_t; };
+// elt.h's make_chunk3 in that form (packing the bf16 values in a uint4 union compiles to other instructions)
+__device__ __forceinline__ cu32x4_t reg_chunk3(float a, float b, float c, bf16_t*) {
+    union { bf16_t h[8]; cu32x4_t u; } t;
+    t.u = cu32x4_t{0u, 0u, 0u, 0u};
+    t.h[0] = (bf16_t)a; t.h[1] = (bf16_t)b; t.h[2] = (bf16_t)c;
+    return t.u;
 }
-__device__ __forceinline__ void mma(f32x16_t& acc, const f32x8_t& a, const f32x8_t& b) {
-    // k-slot j of the 32x32x2 step = channel {j (lanes 0-31), 8+j (lanes 32-63)} of the 16-group:
-    // any consistent k order is a valid reduction order.
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[j], b.v[j], acc, 0, 0, 0);
+__device__ __forceinline__ cu32x8_t reg_chunk3(float a, float b, float c, float*) {
+    return cu32x8_t{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), 0u, 0u, 0u, 0u, 0u};
 }
 
 template <typename T>
@@ -69,40 +59,10 @@ template <int CP> __device__ __forceinline__ int swz(int p, int c) {
     return c ^ ((p / (16 / CP)) & (CP - 1));
 }
 
-template <typename T> __device__ __forceinline__ typename Elt<T>::chunk_t zero_chunk();
-template <> __device__ __forceinline__ cu32x4_t zero_chunk<bf16_t>() { return cu32x4_t{0u, 0u, 0u, 0u}; }
-template <> __device__ __forceinline__ chunk32_t zero_chunk<float>() { return chunk32_t{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; }
-
-__device__ __forceinline__ cu32x4_t make_chunk3(float a, float b, float c, bf16_t*) {
-    union { bf16_t h[8]; cu32x4_t u; } t;
-    t.u = cu32x4_t{0u, 0u, 0u, 0u};
-    t.h[0] = (bf16_t)a; t.h[1] = (bf16_t)b; t.h[2] = (bf16_t)c;
-    return t.u;
-}
-__device__ __forceinline__ chunk32_t make_chunk3(float a, float b, float c, float*) {
-    return chunk32_t{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), 0u, 0u, 0u, 0u, 0u};
-}
-
-__device__ __forceinline__ float to_f(bf16_t v) { return (float)v; }
-__device__ __forceinline__ float to_f(float v) { return v; }
-
-template <typename T> struct Vec4;
-template <> struct __attribute__((aligned(8))) Vec4<bf16_t> { bf16_t v[4]; };
-template <> struct __attribute__((aligned(16))) Vec4<float> { float v[4]; };
-
 __device__ __forceinline__ float act_apply(float v, int act, float slope) {
     if (act == ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == ACT_LEAKY) return v > 0.f ? v : slope * v;
     return v;
-}
-
-// PyTorch upsample_bilinear2d(align_corners=False) source index for scale `inv` = 1/4 (or 1/2: upscale = 2) (basicvsr.py:22)
-__device__ __forceinline__ void bil4(int d, int in_size, int& i0, int& i1, float& l1, float inv) {
-    float s = (d + 0.5f) * inv - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
 }
 
 #ifndef VSR_CONV_ROW_STAGES
@@ -126,7 +86,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(const ConvArgs a) {
     constexpr int TILE_BYTES = NPIX * (CMAX / 8) * CHB;
     constexpr int SLAB_BYTES = COUT * (CMAX / 8) * CHB;
     constexpr int TPS = conv_taps_per_stage<KS, NSRC>(TILE_BYTES, SLAB_BYTES);
-    typedef typename Elt<T>::chunk_t chunk_t;
+    typedef typename RegChunk<T>::chunk_t chunk_t;
     typedef typename Elt<T>::frag_t frag_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -185,8 +145,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(const ConvArgs a) {
                     for (int k = 0; k < 2; ++k) {
                         const int p = p0 + k * NTHREADS;
                         if (p < NPIX) {
-                            *reinterpret_cast<chunk_t*>(lds_in + (p * 2 + swz<2>(p, 0)) * CHB) = make_chunk3(cv[k][0], cv[k][1], cv[k][2], (T*)nullptr);
-                            *reinterpret_cast<chunk_t*>(lds_in + (p * 2 + swz<2>(p, 1)) * CHB) = zero_chunk<T>();
+                            *reinterpret_cast<chunk_t*>(lds_in + (p * 2 + swz<2>(p, 0)) * CHB) = reg_chunk3(cv[k][0], cv[k][1], cv[k][2], (T*)nullptr);
+                            *reinterpret_cast<chunk_t*>(lds_in + (p * 2 + swz<2>(p, 1)) * CHB) = chunk_t{};
                         }
                     }
                 }
@@ -426,7 +386,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(const ConvArgs a) {
                 const long long plane = (long long)a.Hd * a.Wd;
                 float* dst = reinterpret_cast<float*>(a.dst[z]) + (long long)n * a.dst_nstride + (long long)oy * a.Wd + ox;
                 int y0 = 0, y1 = 0, x0 = 0, x1 = 0; float ly = 0.f, lx = 0.f;
-                if (a.base_lr) { const float binv = a.base_scale == 2 ? 0.5f : 0.25f; bil4(oy, a.base_h, y0, y1, ly, binv); bil4(ox, a.base_w, x0, x1, lx, binv); }
+                if (a.base_lr) { const float binv = a.base_scale == 2 ? 0.5f : 0.25f; bil_src(oy, a.base_h, y0, y1, ly, binv); bil_src(ox, a.base_w, x0, x1, lx, binv); }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     if (c >= a.cout_real) break;

@@ -18,6 +18,7 @@
 // conv_wide2_kernel (persistent, LDS-DMA weight slabs two steps ahead; see its header below): 0.88 PFLOP/s at config 3.
 #include <cmath>
 #include <cstdlib>
+#include "elt.h"
 #include "kernels.h"
 #include "../../include/vsrlab_hip.h"
 
@@ -26,28 +27,7 @@ namespace {
 constexpr int TW = 32, RW = 2, TH = 8, NTHREADS = 256;
 constexpr int TWH = TW + 2, THH = TH + 2, NPIX = THH * TWH;
 
-template <typename T> struct WE;
-template <> struct WE<bf16_t> { static constexpr int CHB = 16; typedef bf16x8_t frag_t; typedef uint4 chunk_t; };
-struct wf32x8_t { float v[8]; };
-struct wchunk_t { uint4 a, b; };
-template <> struct WE<float> { static constexpr int CHB = 32; typedef wf32x8_t frag_t; typedef wchunk_t chunk_t; };
-
-__device__ __forceinline__ void wmma(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void wmma(f32x16_t& acc, const wf32x8_t& a, const wf32x8_t& b) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
 __device__ __forceinline__ int wswz(int p, int c) { return c ^ ((p >> 1) & 7); }     // 8 chunks per 64-channel row
-template <typename T> __device__ __forceinline__ typename WE<T>::chunk_t wzero();
-template <> __device__ __forceinline__ uint4 wzero<bf16_t>() { return make_uint4(0, 0, 0, 0); }
-template <> __device__ __forceinline__ wchunk_t wzero<float>() { wchunk_t z; z.a = make_uint4(0, 0, 0, 0); z.b = z.a; return z; }
-__device__ __forceinline__ float wf(bf16_t v) { return (float)v; }
-__device__ __forceinline__ float wf(float v) { return v; }
-template <typename T> struct WV4;
-template <> struct __attribute__((aligned(8))) WV4<bf16_t> { bf16_t v[4]; };
-template <> struct __attribute__((aligned(16))) WV4<float> { float v[4]; };
 
 struct WideArgs {
     const void* x; long long x_nstride; int xC, Hx, Wx;   // source: blocked pixel-major, xC channels per pixel
@@ -69,11 +49,11 @@ struct WideArgs {
 
 template <typename T>
 __global__ __launch_bounds__(NTHREADS) void conv_wide_kernel(const WideArgs a) {
-    constexpr int CHB = WE<T>::CHB;
+    constexpr int CHB = Elt<T>::CHB;
     constexpr int TILE_BYTES = NPIX * 8 * CHB;
     constexpr int SLAB_BYTES = 64 * 8 * CHB;
-    typedef typename WE<T>::chunk_t chunk_t;
-    typedef typename WE<T>::frag_t frag_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::frag_t frag_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* lds_in = smem;
     char* lds_w = smem + TILE_BYTES;
@@ -110,7 +90,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wide_kernel(const WideArgs a) {
             const int p = idx >> 3, c = idx & 7;
             const int ty = p / TWH, tx = p - ty * TWH;
             const int vy = ty0 + ty - 1, vx = tx0 + tx - 1;
-            chunk_t v = wzero<T>();
+            chunk_t v = zero_chunk<T>();
             if (vy >= 0 && vy < a.H && vx >= 0 && vx < a.W) {
                 const int sy = vy * a.in_step + oy, sx = vx * a.in_step + ox;
                 const long long o = (((long long)sy * xws + (sx >> 5)) * xCP + slice * 8 + c) * 256 + (sx & 31) * 8;
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wide_kernel(const WideArgs a) {
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-                    for (int rw = 0; rw < RW; ++rw) wmma(acc[cb][rw], af[cb], bf[rw]);
+                    for (int rw = 0; rw < RW; ++rw) mma(acc[cb][rw], af[cb], bf[rw]);
             }
             if (next < 9) {
                 char* nbuf = lds_w + (buf ^ 1) * SLAB_BYTES;
@@ -206,30 +186,30 @@ __global__ __launch_bounds__(NTHREADS) void conv_wide_kernel(const WideArgs a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
                 }
-                WV4<T> t;
+                Vec4<T> t;
                 if (a.y_act) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) t.v[j] = (T)v[j];
-                    *reinterpret_cast<WV4<T>*>(reinterpret_cast<T*>(a.y_act) + o) = t;
+                    *reinterpret_cast<Vec4<T>*>(reinterpret_cast<T*>(a.y_act) + o) = t;
                 }
                 if (a.res) {
-                    const WV4<T> r = *reinterpret_cast<const WV4<T>*>(reinterpret_cast<const T*>(a.res) + o);
+                    const Vec4<T> r = *reinterpret_cast<const Vec4<T>*>(reinterpret_cast<const T*>(a.res) + o);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] += wf(r.v[j]);
+                    for (int j = 0; j < 4; ++j) v[j] += to_f(r.v[j]);
                 }
                 if (a.y_pre) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) t.v[j] = (T)v[j];
-                    *reinterpret_cast<WV4<T>*>(reinterpret_cast<T*>(a.y_pre) + o) = t;
+                    *reinterpret_cast<Vec4<T>*>(reinterpret_cast<T*>(a.y_pre) + o) = t;
                 }
                 if (a.aux) {
-                    const WV4<T> m = *reinterpret_cast<const WV4<T>*>(reinterpret_cast<const T*>(a.aux) + o);
+                    const Vec4<T> m = *reinterpret_cast<const Vec4<T>*>(reinterpret_cast<const T*>(a.aux) + o);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] *= (wf(m.v[j]) > 0.f ? 1.f : a.slope);
+                    for (int j = 0; j < 4; ++j) v[j] *= (to_f(m.v[j]) > 0.f ? 1.f : a.slope);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) t.v[j] = (T)v[j];
-                *reinterpret_cast<WV4<T>*>(reinterpret_cast<T*>(a.y) + o) = t;
+                *reinterpret_cast<Vec4<T>*>(reinterpret_cast<T*>(a.y) + o) = t;
             }
         }
     }
@@ -651,35 +631,6 @@ __global__ void wgrad_reduce_s2_kernel(const float* __restrict__ slab, int nwg, 
 }
 
 // ---- bilinear x2 (align_corners=False) on blocked pixel-major tensors, and its adjoint ----
-__device__ __forceinline__ void up2_src(int d, int in_size, int& i0, int& i1, float& l1) {
-    float s = ((float)d + 0.5f) * 0.5f - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float* f);
-template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t* p, float* f) {
-    union { uint4 u; bf16_t h[8]; } t; t.u = *reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (float)t.h[j];
-}
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float* f) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, const float* f);
-template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float* f) {
-    union { uint4 u; bf16_t h[8]; } t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.h[j] = (bf16_t)f[j];
-    *reinterpret_cast<uint4*>(p) = t.u;
-}
-template <> __device__ __forceinline__ void st8<float>(float* p, const float* f) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
-
 // out (N, 2H, 2W, C) = up2(a [+ b]);  a, b: (N, H, W, C).  One thread = one SOURCE pixel x 8 channels -> its 2 x 2 output pixels from the
 // clamped 3 x 3 source neighbourhood (x2 bilinear, align_corners=False, is separable with weights (1/4, 3/4) / (3/4, 1/4); at the image
 // border the clamped neighbour carries the missing weight, which is exactly torch's source-index clamp): 2.25 (4.5 with b) 16-byte loads
@@ -952,11 +903,6 @@ __global__ void bce_logits_kernel(const float* __restrict__ x, float* __restrict
     if ((threadIdx.x & 63) == 0) atomicAdd(loss, local * scale);
 }
 
-inline int wgrid(long long total, int block = 256) {
-    long long g = (total + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
-}
-
 }  // namespace
 
 // ======================================= host side (C++ linkage, used by disc_engine.hip) ==================================
@@ -1097,8 +1043,8 @@ int vsr_launch_up2_bwd(int dtype, const void* dout, void* din, void* dmask, cons
 
 int vsr_launch_add_pm(int dtype, const void* a, const void* b, void* out, long long elems, hipStream_t st) {
     const long long n8 = elems / 8;
-    if (dtype == VSR_BF16) hipLaunchKernelGGL(add_pm_kernel<bf16_t>, dim3(wgrid(n8)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n8);
-    else if (dtype == VSR_F32) hipLaunchKernelGGL(add_pm_kernel<float>, dim3(wgrid(n8)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n8);
+    if (dtype == VSR_BF16) hipLaunchKernelGGL(add_pm_kernel<bf16_t>, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n8);
+    else if (dtype == VSR_F32) hipLaunchKernelGGL(add_pm_kernel<float>, dim3(grid_for(n8)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n8);
     else return VSR_ERR_BADARG;
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
@@ -1106,8 +1052,8 @@ int vsr_launch_add_pm(int dtype, const void* a, const void* b, void* out, long l
 
 int vsr_launch_mask_pm(int dtype, const void* g, const void* m, void* out, float slope, long long elems, hipStream_t st) {
     const long long n8 = elems / 8;
-    if (dtype == VSR_BF16) hipLaunchKernelGGL(mask_pm_kernel<bf16_t>, dim3(wgrid(n8)), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)m, (bf16_t*)out, slope, n8);
-    else if (dtype == VSR_F32) hipLaunchKernelGGL(mask_pm_kernel<float>, dim3(wgrid(n8)), dim3(256), 0, st, (const float*)g, (const float*)m, (float*)out, slope, n8);
+    if (dtype == VSR_BF16) hipLaunchKernelGGL(mask_pm_kernel<bf16_t>, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)m, (bf16_t*)out, slope, n8);
+    else if (dtype == VSR_F32) hipLaunchKernelGGL(mask_pm_kernel<float>, dim3(grid_for(n8)), dim3(256), 0, st, (const float*)g, (const float*)m, (float*)out, slope, n8);
     else return VSR_ERR_BADARG;
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
@@ -1127,7 +1073,7 @@ int vsr_spectral_norm(const float* w_orig, float* u, float* v, float* w_out, flo
     hipLaunchKernelGGL(sn_norm_kernel, dim3(1), dim3(1024), 0, st, v, cols, 1e-12f, (float*)nullptr);
     hipLaunchKernelGGL(sn_wv_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, w_orig, (const float*)v, u, rows, cols);
     hipLaunchKernelGGL(sn_norm_kernel, dim3(1), dim3(1024), 0, st, u, rows, 1e-12f, sigma);
-    hipLaunchKernelGGL(sn_scale_kernel, dim3(wgrid((long long)rows * cols)), dim3(256), 0, st, w_orig, (const float*)sigma, w_out, (long long)rows * cols);
+    hipLaunchKernelGGL(sn_scale_kernel, dim3(grid_for((long long)rows * cols)), dim3(256), 0, st, w_orig, (const float*)sigma, w_out, (long long)rows * cols);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
 }
@@ -1140,7 +1086,7 @@ int vsr_spectral_norm_backward(const float* dw, const float* w_orig, const float
     int parts = (int)((n + 256 * 64 - 1) / (256 * 64));
     if (parts > VSR_SN_SCRATCH_FLOATS) parts = VSR_SN_SCRATCH_FLOATS;
     hipLaunchKernelGGL(sn_bwd_dot_kernel, dim3(parts), dim3(256), 0, st, dw, w_orig, scratch, n);
-    hipLaunchKernelGGL(sn_bwd_apply_kernel, dim3(wgrid(n)), dim3(256), 0, st, dw, u, v, sigma, (const float*)scratch, parts, dw_orig, rows, cols);
+    hipLaunchKernelGGL(sn_bwd_apply_kernel, dim3(grid_for(n)), dim3(256), 0, st, dw, u, v, sigma, (const float*)scratch, parts, dw_orig, rows, cols);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
 }
@@ -1149,7 +1095,7 @@ int vsr_bce_with_logits(const float* x, float target, float* dx, float* loss, lo
     if (!x || !loss || numel < 1) return VSR_ERR_BADARG;
     hipStream_t st = (hipStream_t)stream;
     HIP_CHECK_RET(hipMemsetAsync(loss, 0, sizeof(float), st));
-    hipLaunchKernelGGL(bce_logits_kernel, dim3(wgrid(numel)), dim3(256), 0, st, x, dx, loss, numel, target, 1.0f / (float)numel);
+    hipLaunchKernelGGL(bce_logits_kernel, dim3(grid_for(numel)), dim3(256), 0, st, x, dx, loss, numel, target, 1.0f / (float)numel);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
 }

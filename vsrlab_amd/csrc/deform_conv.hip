@@ -15,6 +15,7 @@
 // Weight gradient: workgroup = (tap, pixel part); it gathers a 64-pixel column tile and the dY tile to LDS (pixels contiguous:
 // the K index of this product) and keeps all Cout x Cin accumulator blocks of its tap in registers; partial slabs + a reduction
 // launch in a fixed order (bit-identical across runs), as wgrad_mfma.hip does.
+#include "elt.h"
 #include "host.h"
 
 namespace {
@@ -27,27 +28,14 @@ constexpr int DC_WROW = DC_WPIX + 8;    // LDS row (elements): 16-byte aligned r
 constexpr int DC_WPARTS = 56;           // pixel parts of the weight gradient: 9 taps x 56 = 504 workgroups
 constexpr int DC_WMAXB = 9;             // accumulator blocks per wave: 36 / 4
 
-struct f32x8 { float v[8]; };
-template <typename T> struct Tr;
-template <> struct Tr<bf16_t> { typedef bf16x8_t frag; };
-template <> struct Tr<float> { typedef f32x8 frag; };
-
-__device__ __forceinline__ void mma(f32x16_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma(f32x16_t& acc, const f32x8& a, const f32x8& b) {
-    // k slot j of a 32x32x2 step = element j of either lane half: any consistent k order is a valid reduction order
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
 __device__ __forceinline__ void put(bf16x8_t& f, int i, float v) { f[i] = (bf16_t)v; }
-__device__ __forceinline__ void put(f32x8& f, int i, float v) { f.v[i] = v; }
+__device__ __forceinline__ void put(f32x8_t& f, int i, float v) { f.v[i] = v; }
 __device__ __forceinline__ float get(const bf16x8_t& f, int i) { return (float)f[i]; }
-__device__ __forceinline__ float get(const f32x8& f, int i) { return f.v[i]; }
+__device__ __forceinline__ float get(const f32x8_t& f, int i) { return f.v[i]; }
 __device__ __forceinline__ bf16_t elem(const bf16x8_t& f, int i) { return f[i]; }
-__device__ __forceinline__ float elem(const f32x8& f, int i) { return f.v[i]; }
-template <typename T> __device__ __forceinline__ typename Tr<T>::frag load8(const T* p) {
-    return *reinterpret_cast<const typename Tr<T>::frag*>(p);
+__device__ __forceinline__ float elem(const f32x8_t& f, int i) { return f.v[i]; }
+template <typename T> __device__ __forceinline__ typename Elt<T>::frag_t load8(const T* p) {
+    return *reinterpret_cast<const typename Elt<T>::frag_t*>(p);
 }
 __device__ __forceinline__ void load4(const float* p, float* v) {
     const f32x4_t t = *reinterpret_cast<const f32x4_t*>(p);
@@ -121,18 +109,18 @@ __device__ __forceinline__ void setup(const DeformArgs& a, int n, int g, int k, 
 
 // 8 channels of the column of one pixel: (bilinear sample) * mask, rounded to T
 template <typename T>
-__device__ __forceinline__ typename Tr<T>::frag gather8(const T* img, int XC, int c, const Samp& s) {
+__device__ __forceinline__ typename Elt<T>::frag_t gather8(const T* img, int XC, int c, const Samp& s) {
     const auto a = load8<T>(img + (long long)s.o00 * XC + c), b = load8<T>(img + (long long)s.o01 * XC + c);
     const auto d = load8<T>(img + (long long)s.o10 * XC + c), e = load8<T>(img + (long long)s.o11 * XC + c);
-    typename Tr<T>::frag f;
+    typename Elt<T>::frag_t f;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
         put(f, i, (s.w00 * get(a, i) + s.w01 * get(b, i) + s.w10 * get(d, i) + s.w11 * get(e, i)) * s.m);
     return f;
 }
 
-template <typename T> __device__ __forceinline__ typename Tr<T>::frag zero_frag() {
-    typename Tr<T>::frag f;
+template <typename T> __device__ __forceinline__ typename Elt<T>::frag_t zero_frag() {
+    typename Elt<T>::frag_t f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) put(f, i, 0.f);
     return f;
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(256) void deform_fwd_kernel(DeformArgs a) {
         Samp s;
         for (int kc = 0; kc < nkc; ++kc) {
             const int c = kc * 16 + 8 * h, g = c / a.cpgp;      // this lane's 8 channels and their group
-            typename Tr<T>::frag b = zero_frag<T>();
+            typename Elt<T>::frag_t b = zero_frag<T>();
             if (g < a.dg) {
                 if (g != curg) { curg = g; setup(a, n, g, k, p, y, x, fy, fx, s); }
                 b = gather8<T>(img, a.XC, c, s);
@@ -201,7 +189,7 @@ __global__ __launch_bounds__(256) void deform_bwd_kernel(DeformArgs a) {
     float fy = 0.f, fx = 0.f;
     if (a.flow_guided) { fx = a.flow[((long long)n * 2) * HW + p]; fy = a.flow[((long long)n * 2 + 1) * HW + p]; }
     const int noc = a.CoutP / 16, ncb = a.XC / 32;
-    typename Tr<T>::frag dyf[DC_MAXOC];                    // B[k = cout 16 oc + 8 h + e][pixel]
+    typename Elt<T>::frag_t dyf[DC_MAXOC];                    // B[k = cout 16 oc + 8 h + e][pixel]
 #pragma unroll
     for (int oc = 0; oc < DC_MAXOC; ++oc)
 #pragma unroll
@@ -314,7 +302,7 @@ __global__ __launch_bounds__(256) void deform_wgrad_kernel(DeformArgs a) {
             Samp s;
             for (int c8 = wave; c8 < a.XC / 8; c8 += 4) {
                 const int c = 8 * c8, g = c / a.cpgp;
-                typename Tr<T>::frag f = zero_frag<T>();
+                typename Elt<T>::frag_t f = zero_frag<T>();
                 if (g < a.dg && pv) {
                     if (g != curg) { curg = g; setup(a, n, g, k, p, y, x, fy, fx, s); }
                     f = gather8<T>(img, a.XC, c, s);

@@ -2,34 +2,10 @@
 // the SPyNet pyramid plumbing (resize, normalise, average-pool, per-level warp+concat, flow
 // upsample), weight packing and small glue.  All are pure streaming kernels: one pass, 16-byte
 // accesses on pixel-major tensors, planar fp32 accesses coalesced along x.
+#include "elt.h"
 #include "kernels.h"
 
 namespace {
-
-template <typename T> struct EW;
-template <> struct EW<bf16_t> { typedef uint4 chunk_t; };
-struct echunk32_t { uint4 a, b; };
-template <> struct EW<float> { typedef echunk32_t chunk_t; };
-
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-    union { uint4 u; bf16_t h[8]; } t; t.u = v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (float)t.h[j];
-}
-__device__ __forceinline__ void unpack8(const echunk32_t& v, float* f) {
-    f[0] = __uint_as_float(v.a.x); f[1] = __uint_as_float(v.a.y); f[2] = __uint_as_float(v.a.z); f[3] = __uint_as_float(v.a.w);
-    f[4] = __uint_as_float(v.b.x); f[5] = __uint_as_float(v.b.y); f[6] = __uint_as_float(v.b.z); f[7] = __uint_as_float(v.b.w);
-}
-__device__ __forceinline__ void pack8(const float* f, uint4& v) {
-    union { uint4 u; bf16_t h[8]; } t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.h[j] = (bf16_t)f[j];
-    v = t.u;
-}
-__device__ __forceinline__ void pack8(const float* f, echunk32_t& v) {
-    v.a = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-    v.b = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]), __float_as_uint(f[6]), __float_as_uint(f[7]));
-}
 
 // Sample position of flow_warp (spynet.py:95-106).  The reference normalises the pixel grid to
 // [-1,1] and grid_sample(align_corners=True) maps it back; we reproduce that round trip so the
@@ -44,7 +20,7 @@ __device__ __forceinline__ float warp_coord(float base, float flow, int dim) {
 template <typename T>
 __global__ void warp_fwd_kernel(const T* __restrict__ in, const float* __restrict__ flow, T* __restrict__ out,
                                 int N, int H, int W, int C, long long flow_nstride, int border) {
-    typedef typename EW<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
     const int CP = C / 8;
     const long long total = (long long)N * H * W * CP;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const T* __restric
                                                               long long* __restrict__ S, const int* __restrict__ far_count, T* __restrict__ out,
                                                               int N, int H, int W, long long flow_nstride) {
     constexpr int CP = C / 8, PPP = 256 / CP;          // chunks per pixel, destination pixels per pass
-    typedef typename EW<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
     __shared__ float2 pos[GHH * GHW];                   // sample position of each source of the haloed tile; x = NaN: far / outside
     __shared__ unsigned short hit_src[256 * GCAP];
     __shared__ float hit_w[256 * GCAP];
@@ -318,7 +294,7 @@ __global__ void warp_bwd_far_kernel(const T* __restrict__ dout, const float* __r
 // accumulator) or null.  One thread per (pixel, 8-channel chunk).
 template <typename T>
 __global__ void add_cast_kernel(const T* __restrict__ a, const float* __restrict__ s, T* __restrict__ out, int N, int H, int W, int C) {
-    typedef typename EW<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
     const int CP = C / 8;
     const long long total = (long long)N * H * W * CP;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -467,13 +443,13 @@ __global__ void spynet_prepare_kernel(const float* __restrict__ frames, const fl
             v[3 + c] = wy0 * (wx0 * sp[y0 * w + x0] + wx1 * sp[y0 * w + x1]) + wy1 * (wx0 * sp[y1 * w + x0] + wx1 * sp[y1 * w + x1]);
         }
         v[6] = fu[0]; v[7] = fu[1];
-        typename EW<T>::chunk_t lo, hi;
+        typename Elt<T>::chunk_t lo, hi;
         float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         pack8(v, lo);
         pack8(z, hi);
         T* o = x16 + (long long)p * pm_image_elems(h, w, 16);
-        *reinterpret_cast<typename EW<T>::chunk_t*>(o + pm_off(y, x, 0, w, 16)) = lo;
-        *reinterpret_cast<typename EW<T>::chunk_t*>(o + pm_off(y, x, 1, w, 16)) = hi;
+        *reinterpret_cast<typename Elt<T>::chunk_t*>(o + pm_off(y, x, 0, w, 16)) = lo;
+        *reinterpret_cast<typename Elt<T>::chunk_t*>(o + pm_off(y, x, 1, w, 16)) = hi;
     }
 }
 
@@ -504,7 +480,7 @@ __global__ void flow_out_kernel(const float* __restrict__ in, float* __restrict_
 template <typename T>
 __global__ void warp_bwd_flow_kernel(const T* __restrict__ in, const T* __restrict__ dout, const float* __restrict__ flow,
                                      float* __restrict__ dflow, int N, int H, int W, int C, long long flow_nstride, int border) {
-    typedef typename EW<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
     const int CP = C / 8;
     const long long total = (long long)N * H * W;
     for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < total; pix += (long long)gridDim.x * blockDim.x) {
@@ -565,12 +541,12 @@ __global__ void spynet_dres_kernel(const float* __restrict__ dflow, const float*
         float v[8] = {0, 0, 0, 0, 0, 0, 0, 0}, z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         v[0] = (!res || res[o] > 0.f) ? dflow[o] : 0.f;             // res == NULL: no ReLU behind the last conv (the canonical SPyNet of the VRT tree)
         v[1] = (!res || res[o + hw] > 0.f) ? dflow[o + hw] : 0.f;
-        typename EW<T>::chunk_t lo, hi;
+        typename Elt<T>::chunk_t lo, hi;
         pack8(v, lo);
         pack8(z, hi);
         T* ob = out + p * pm_image_elems(h, w, 16);
-        *reinterpret_cast<typename EW<T>::chunk_t*>(ob + pm_off(y, x, 0, w, 16)) = lo;
-        *reinterpret_cast<typename EW<T>::chunk_t*>(ob + pm_off(y, x, 1, w, 16)) = hi;
+        *reinterpret_cast<typename Elt<T>::chunk_t*>(ob + pm_off(y, x, 0, w, 16)) = lo;
+        *reinterpret_cast<typename Elt<T>::chunk_t*>(ob + pm_off(y, x, 1, w, 16)) = hi;
     }
 }
 
@@ -605,7 +581,7 @@ __global__ void spynet_prepare_bwd_kernel(const T* __restrict__ dx16, const floa
             fsup = p < half ? b * t + i + 1 : b * t + i;
         }
         float d[8];
-        unpack8(*reinterpret_cast<const typename EW<T>::chunk_t*>(dx16 + (long long)p * pm_image_elems(h, w, 16) + pm_off(y, x, 0, w, 16)), d);
+        unpack8(*reinterpret_cast<const typename Elt<T>::chunk_t*>(dx16 + (long long)p * pm_image_elems(h, w, 16) + pm_off(y, x, 0, w, 16)), d);
         const float fu0 = flow_up ? flow_up[((long long)p * 2 + 0) * hw + (long long)y * w + x] : 0.f;   // level 0: flow_up = 0
         const float fu1 = flow_up ? flow_up[((long long)p * 2 + 1) * hw + (long long)y * w + x] : 0.f;
         float px = warp_coord((float)x, fu0, w), py = warp_coord((float)y, fu1, h);
@@ -862,11 +838,6 @@ __global__ void charbonnier_sum_kernel(const float* __restrict__ partial, int nb
         __syncthreads();
     }
     if (threadIdx.x == 0) loss[0] = red[0];
-}
-
-inline int grid_for(long long total, int block = 256) {
-    long long g = (total + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
 }
 
 }  // namespace

@@ -2,6 +2,7 @@
 // streaming problem, not a GEMM.  Dedicated bf16 kernels for the HR tail of the backward pass (the generic tiled
 // kernel pads 3 channels to 16/32 and synchronises per tap: 0.9 ms per frame at 2160x3840 against an HBM floor of ~0.45).
 #include "conv3x3_c64_tile.h"      // c64_sign_word: the sign bits are read in the 3x3 kernels' tile order
+#include "elt.h"
 #include "kernels.h"
 #include <type_traits>
 
@@ -213,15 +214,6 @@ __global__ __launch_bounds__(LT_NT) void last2_dgrad_kernel(const float* __restr
     }
 }
 
-// PyTorch upsample_bilinear2d(align_corners=False) source index for scale `inv` = 1/4 (or 1/2: upscale = 2) (basicvsr.py:22)
-__device__ __forceinline__ void hr_bil4(int d, int in_size, int& i0, int& i1, float& l1, float inv = 0.25f) {
-    float s = (d + 0.5f) * inv - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
-
 // conv3x3 64 -> (<= 4) channels with a planar fp32 destination: conv_last.2 + bilinear x4 skip (basicvsr.py:21-22,82),
 // the pre-clean stack's `x + conv` (realbasicvsr.py:28-29), the stems' LR-channel data gradient.  M = 16 rows (<= 4
 // real) x N = 16 pixels x K = 32 channels per v_mfma_f32_16x16x32_bf16: all 18 (tap, channel-half) weight fragments live
@@ -313,7 +305,7 @@ __global__ __launch_bounds__(FP_NT, 1) void c64_to_planar_kernel(const ConvArgs 
     // The BasicVSR case (conv_last.2 + bilinear x4 skip, 3 channels, an LR frame of exactly H/4 x W/4) without per-tile divisions,
     // float index arithmetic or per-channel branches (r03: the tile time of this kernel is set by its consumers).  For d = 4 m + r,
     // (d + 0.5) / 4 - 0.5 = m + (r - 1.5) / 4: source index m - 1 (r < 2) or m, weight 0.625 / 0.875 / 0.125 / 0.375 -- exactly what
-    // hr_bil4 computes in fp32; tile origins are multiples of 8 and 32, so r and the weight are per-lane constants.
+    // bil_src computes in fp32; tile origins are multiples of 8 and 32, so r and the weight are per-lane constants.
     const int oyr = 2 * w4 + (q >> 1), oxr = (q & 1) * 16 + px15;
     const int yk = (oyr >> 2) - ((oyr & 3) < 2 ? 1 : 0), xk = (oxr >> 2) - ((oxr & 3) < 2 ? 1 : 0);
     const float wq[4] = {0.625f, 0.875f, 0.125f, 0.375f};
@@ -366,7 +358,7 @@ __global__ __launch_bounds__(FP_NT, 1) void c64_to_planar_kernel(const ConvArgs 
             ly = lyn; lx = lxn;
         } else if (ok) {
             int y0 = 0, y1 = 0, x0 = 0, x1 = 0; float ly = 0.f, lx = 0.f;
-            if (a.base_lr) { hr_bil4(oy, a.base_h, y0, y1, ly, binv); hr_bil4(ox, a.base_w, x0, x1, lx, binv); }
+            if (a.base_lr) { bil_src(oy, a.base_h, y0, y1, ly, binv); bil_src(ox, a.base_w, x0, x1, lx, binv); }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (c >= a.cout_real) break;
@@ -442,9 +434,6 @@ constexpr int LW_ROW = 8 * LW_XS * 16, LW_TILE = (LT_H + 2) * LW_ROW;  // 4,608 
 constexpr int LW_SLOTS = LW_TILE / 16, LW_NPIECE = LW_SLOTS / 64;      // 2,880 slots = 45 DMA pieces
 constexpr int LW_NPIECE_W = (LW_NPIECE + 3) / 4;                       // 12 per producer wave
 constexpr int LW_DY = 3 * LT_H * LT_W * 4;                             // 3,072 bytes: the dY tile of the ring kernel
-__device__ __forceinline__ s16x4_t hr_tr_read(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
-}
 
 __global__ __launch_bounds__(FP_NT, 1) void last2_wgrad_kernel(const bf16_t* __restrict__ x, const float* __restrict__ dy,
                                                                long long dy_nstride, float* __restrict__ slab, int slab_stride,
@@ -540,8 +529,8 @@ __global__ __launch_bounds__(FP_NT, 1) void last2_wgrad_kernel(const bf16_t* __r
                 for (int mb = 0; mb < 4; ++mb) {
                     const char* pa = tb + (2 * w4 + rr + tap / 3) * LW_ROW + mb * 2 * (LW_XS * 16) + (tap % 3) * 16;
                     union { s16x4_t s[2]; bf16x8_t b; } u;
-                    u.s[0] = hr_tr_read(pa);
-                    u.s[1] = hr_tr_read(pa + 64);
+                    u.s[0] = lds_tr_read(pa);
+                    u.s[1] = lds_tr_read(pa + 64);
                     acc[tap][mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.b, fb[rr], acc[tap][mb], 0, 0, 0);
                 }
         __syncthreads();                                     // the producers' next tile has landed; this one is consumed

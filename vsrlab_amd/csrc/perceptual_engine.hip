@@ -17,6 +17,7 @@
 // the hr tap), and the data-gradient chain runs from conv5_4 down to the planar fp32 d sr.  Each backward layer writes into the
 // buffer of an activation that is no longer needed, so the backward needs no scratch of its own.
 #include <vector>
+#include "elt.h"
 #include "host.h"
 
 namespace {
@@ -32,28 +33,6 @@ constexpr int L_LV[NCONV] = {0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4};
 constexpr int TAP_CONV[NTAP] = {1, 3, 7, 11, 15};      // conv (by position) whose output is tap '2', '7', '16', '25', '34'
 
 // ============================================== kernels =============================================================
-template <typename T> __device__ __forceinline__ void pld8(const T* p, float* f);
-template <> __device__ __forceinline__ void pld8<bf16_t>(const bf16_t* p, float* f) {
-    union { uint4 u; bf16_t h[8]; } t; t.u = *reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (float)t.h[j];
-}
-template <> __device__ __forceinline__ void pld8<float>(const float* p, float* f) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename T> __device__ __forceinline__ void pst8(T* p, const float* f);
-template <> __device__ __forceinline__ void pst8<bf16_t>(bf16_t* p, const float* f) {
-    union { uint4 u; bf16_t h[8]; } t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.h[j] = (bf16_t)f[j];
-    *reinterpret_cast<uint4*>(p) = t.u;
-}
-template <> __device__ __forceinline__ void pst8<float>(float* p, const float* f) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
-
 // out (N, Hi/2, Wi/2, C) = MaxPool2d(2, 2)(in (N, Hi, Wi, C)), floor sizes.  One thread = one output pixel x 8 channels;
 // consecutive lanes = consecutive pixels of a 32-pixel output segment (the store is one 512-byte run).
 template <typename T>
@@ -67,17 +46,17 @@ __global__ void maxpool2_fwd_kernel(const T* __restrict__ in, T* __restrict__ ou
     if (x >= Wo) return;
     const T* ib = in + (long long)n * pm_image_elems(Hi, Wi, C);
     float m[8], v[8];
-    pld8<T>(ib + pm_off(2 * y, 2 * x, c, Wi, C), m);
-    pld8<T>(ib + pm_off(2 * y, 2 * x + 1, c, Wi, C), v);
+    ld8<T>(ib + pm_off(2 * y, 2 * x, c, Wi, C), m);
+    ld8<T>(ib + pm_off(2 * y, 2 * x + 1, c, Wi, C), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
-    pld8<T>(ib + pm_off(2 * y + 1, 2 * x, c, Wi, C), v);
+    ld8<T>(ib + pm_off(2 * y + 1, 2 * x, c, Wi, C), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
-    pld8<T>(ib + pm_off(2 * y + 1, 2 * x + 1, c, Wi, C), v);
+    ld8<T>(ib + pm_off(2 * y + 1, 2 * x + 1, c, Wi, C), v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
-    pst8<T>(out + (long long)n * pm_image_elems(Ho, Wo, C) + pm_off(y, x, c, Wo, C), m);
+    st8<T>(out + (long long)n * pm_image_elems(Ho, Wo, C) + pm_off(y, x, c, Wo, C), m);
 }
 
 // Backward of MaxPool2d(2, 2) fused with the tap cotangent and the ReLU in front of the pool:
@@ -105,9 +84,9 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ a, const T* __restrict
         for (int j = 0; j < 8; ++j) route[q][j] = 0.f;
     if (inside) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) pld8<T>(ab + pm_off(2 * by + (q >> 1), 2 * bx + (q & 1), c, Wi, C), av[q]);
+        for (int q = 0; q < 4; ++q) ld8<T>(ab + pm_off(2 * by + (q >> 1), 2 * bx + (q & 1), c, Wi, C), av[q]);
         float d[8];
-        pld8<T>(dp + (long long)n * pm_image_elems(Ho, Wo, C) + pm_off(by, bx, c, Wo, C), d);
+        ld8<T>(dp + (long long)n * pm_image_elems(Ho, Wo, C) + pm_off(by, bx, c, Wo, C), d);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             int arg = 0;
@@ -124,16 +103,16 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ a, const T* __restrict
         if (y >= Hi || x >= Wi) continue;
         const long long o = pm_off(y, x, c, Wi, C);
         float gv[8], m[8];
-        pld8<T>(gb + o, gv);
+        ld8<T>(gb + o, gv);
         if (inside) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) m[j] = av[q][j];
         } else {
-            pld8<T>(ab + o, m);
+            ld8<T>(ab + o, m);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) gv[j] = m[j] > 0.f ? gv[j] + route[q][j] : 0.f;
-        pst8<T>(gb + o, gv);
+        st8<T>(gb + o, gv);
     }
 }
 
@@ -154,8 +133,8 @@ __global__ __launch_bounds__(TAP_NT) void tap_l1_kernel(const T* __restrict__ s,
         const int seg = (int)((i >> 5) / CP % WS);
         if (seg * 32 + px >= W) continue;                                  // padding pixels are never written: skip them
         float a[8], b[8];
-        pld8<T>(s + img + i * 8, a);
-        pld8<T>(h + img + i * 8, b);
+        ld8<T>(s + img + i * 8, a);
+        ld8<T>(h + img + i * 8, b);
         float part = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(TAP_NT) void tap_l1_kernel(const T* __restrict__ s,
             b[j] = d > 0.f ? scale : (d < 0.f ? -scale : 0.f);
         }
         acc += (double)part;
-        if (g) pst8<T>(g + img + i * 8, b);
+        if (g) st8<T>(g + img + i * 8, b);
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
     __shared__ double red[TAP_NT / 64];

@@ -13,34 +13,21 @@
 // (gridDim x 147 KB) small against the activations streamed (t x 132 MB for a 540p trunk conv).
 // The bias gradient rides along: column sums of dY accumulated while staging dY.
 #include <cstdlib>
+#include "elt.h"
 #include "kernels.h"
 
 namespace {
 
 constexpr int TW = 32, TH = 8, NTHREADS = 256;
 
-template <typename T> struct WElt;
-template <> struct WElt<bf16_t> { static constexpr int CHB = 16; typedef uint4 chunk_t; };
-struct wchunk32_t { uint4 a, b; };
-template <> struct WElt<float> { static constexpr int CHB = 32; typedef wchunk32_t chunk_t; };
-
-template <typename T> __device__ __forceinline__ typename WElt<T>::chunk_t wzero();
-template <> __device__ __forceinline__ uint4 wzero<bf16_t>() { return make_uint4(0, 0, 0, 0); }
-template <> __device__ __forceinline__ wchunk32_t wzero<float>() { wchunk32_t z; z.a = make_uint4(0, 0, 0, 0); z.b = z.a; return z; }
-
-__device__ __forceinline__ uint4 wchunk3(float a, float b, float c, bf16_t*) {
-    union { bf16_t h[8]; uint4 u; } t; t.u = make_uint4(0, 0, 0, 0);
-    t.h[0] = (bf16_t)a; t.h[1] = (bf16_t)b; t.h[2] = (bf16_t)c; return t.u;
-}
-__device__ __forceinline__ wchunk32_t wchunk3(float a, float b, float c, float*) {
-    wchunk32_t t; t.a = make_uint4(__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), 0); t.b = make_uint4(0, 0, 0, 0); return t;
-}
+// column sums of dY (the bias gradient): s[0..8) += the 8 channels of a loaded chunk (unpack8 into a temporary and an add
+// compile to other register allocations, so the sum is spelled out)
 __device__ __forceinline__ void chunk_sum(const uint4& v, float* s) {
     union { uint4 u; bf16_t h[8]; } t; t.u = v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] += (float)t.h[j];
 }
-__device__ __forceinline__ void chunk_sum(const wchunk32_t& v, float* s) {
+__device__ __forceinline__ void chunk_sum(const chunk32_t& v, float* s) {
     s[0] += __uint_as_float(v.a.x); s[1] += __uint_as_float(v.a.y); s[2] += __uint_as_float(v.a.z); s[3] += __uint_as_float(v.a.w);
     s[4] += __uint_as_float(v.b.x); s[5] += __uint_as_float(v.b.y); s[6] += __uint_as_float(v.b.z); s[7] += __uint_as_float(v.b.w);
 }
@@ -53,12 +40,8 @@ template <int CP> __device__ __forceinline__ int wswz(int pix, int c) {
 
 // byte address of channel `ch` (multiple of 4 for tr reads) of pixel `pix`
 template <typename T, int CP> __device__ __forceinline__ int lds_addr(int pix, int ch) {
-    constexpr int CHB = WElt<T>::CHB;
+    constexpr int CHB = Elt<T>::CHB;
     return (pix * CP + wswz<CP>(pix, ch >> 3)) * CHB + (ch & 7) * (int)sizeof(T);
-}
-
-__device__ __forceinline__ s16x4_t tr_read(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
 }
 
 __device__ uint4 g_wg_zero[4];      // 64 zero bytes: the source of every out-of-image chunk of the generic kernel's staging loops
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
     constexpr int PAD = KS / 2, KK = KS * KS;
     constexpr int TWH = TW + KS - 1, THH = TH + KS - 1, NPIXX = THH * TWH, NPIXY = TH * TW;
     constexpr int CPX = CX / 8, CPY = COUT / 8;
-    constexpr int CHB = WElt<T>::CHB;
+    constexpr int CHB = Elt<T>::CHB;
     constexpr int NCB = COUT >= 32 ? COUT / 32 : 1;
     constexpr int NIB = CX >= 32 ? CX / 32 : 1;
     constexpr int NT = NCB * NIB;                 // (cout-block, cin-block) pairs: 1, 2 or 4
@@ -81,7 +64,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
     constexpr int NTAP = (KT + TAPSPLIT - 1) / TAPSPLIT;
     constexpr int COUTP = NCB * 32, CXP = NIB * 32;
     constexpr int XBYTES = NPIXX * CPX * CHB;
-    typedef typename WElt<T>::chunk_t chunk_t;
+    typedef typename Elt<T>::chunk_t chunk_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* lx = smem;
@@ -130,8 +113,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
                     for (int k = 0; k < 2; ++k) {
                         const int p = p0 + k * NTHREADS;
                         if (p < NPIXX) {
-                            *reinterpret_cast<chunk_t*>(lx + (p * 2 + 0) * CHB) = wchunk3(cv[k][0], cv[k][1], cv[k][2], (T*)nullptr);
-                            *reinterpret_cast<chunk_t*>(lx + (p * 2 + 1) * CHB) = wzero<T>();
+                            *reinterpret_cast<chunk_t*>(lx + (p * 2 + 0) * CHB) = make_chunk3(cv[k][0], cv[k][1], cv[k][2], (T*)nullptr);
+                            *reinterpret_cast<chunk_t*>(lx + (p * 2 + 1) * CHB) = zero_chunk<T>();
                         }
                     }
                 }
@@ -175,8 +158,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
                     const float* sp = in ? base + (long long)(vy * a.dy_step + a.dy_oy) * a.Wy + (vx * a.dy_step + a.dy_ox) : zf;
                     const float c0 = sp[0], c1 = *(in && pc > 1 ? sp + plane : zf), c2 = *(in && pc > 2 ? sp + 2 * plane : zf);   // unconditional loads
                     bsum[0] += c0; bsum[1] += c1; bsum[2] += c2;
-                    *reinterpret_cast<chunk_t*>(ly + (p * 2 + 0) * CHB) = wchunk3(c0, c1, c2, (T*)nullptr);
-                    *reinterpret_cast<chunk_t*>(ly + (p * 2 + 1) * CHB) = wzero<T>();
+                    *reinterpret_cast<chunk_t*>(ly + (p * 2 + 0) * CHB) = make_chunk3(c0, c1, c2, (T*)nullptr);
+                    *reinterpret_cast<chunk_t*>(ly + (p * 2 + 1) * CHB) = zero_chunk<T>();
                 }
             } else {
                 const T* base = reinterpret_cast<const T*>(a.dy[seg]) + (long long)n * a.dy_nstride;
@@ -217,8 +200,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
                         const int chy = cb * 32 + (COUT >= 32 ? 16 * g2 : 0) + p4;
                         const int chx = ib * 32 + (CX >= 32 ? 16 * g2 : 0) + p4;
                         const int py = row * TW + xk + 8 * h + q;
-                        const s16x4_t a0 = tr_read(ly + lds_addr<T, CPY>(py, chy));
-                        const s16x4_t a1 = tr_read(ly + lds_addr<T, CPY>(py + 4, chy));
+                        const s16x4_t a0 = lds_tr_read(ly + lds_addr<T, CPY>(py, chy));
+                        const s16x4_t a1 = lds_tr_read(ly + lds_addr<T, CPY>(py + 4, chy));
                         bf16x8_t af;
                         { union { s16x4_t s[2]; bf16x8_t b; } u; u.s[0] = a0; u.s[1] = a1; af = u.b; }
 #pragma unroll
@@ -227,8 +210,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
                             if (tap0 + i * TAPSPLIT < KT) {
                                 const int ky = tap / KS, kx = tap - ky * KS;
                                 const int px = (row + ky) * TWH + xk + kx + 8 * h + q;
-                                const s16x4_t b0 = tr_read(lx + lds_addr<T, CPX>(px, chx));
-                                const s16x4_t b1 = tr_read(lx + lds_addr<T, CPX>(px + 4, chx));
+                                const s16x4_t b0 = lds_tr_read(lx + lds_addr<T, CPX>(px, chx));
+                                const s16x4_t b1 = lds_tr_read(lx + lds_addr<T, CPX>(px + 4, chx));
                                 union { s16x4_t s[2]; bf16x8_t b; } u; u.s[0] = b0; u.s[1] = b1;
                                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, u.b, acc[i], 0, 0, 0);
                             }
@@ -373,7 +356,7 @@ __global__ void wgrad_reduce_pairs_kernel(const float* __restrict__ slab, int sl
 template <typename T, int KS, int CX, bool XP, int COUT, bool DP>
 int launch_wgrad_inst(const WgradArgs& a0, int nwg, hipStream_t st) {
     constexpr int TWH = TW + KS - 1, THH = TH + KS - 1;
-    constexpr int CHB = WElt<T>::CHB;
+    constexpr int CHB = Elt<T>::CHB;
     constexpr int LDS_T = THH * TWH * (CX / 8) * CHB + TH * TW * (COUT / 8) * CHB;
     constexpr int LDS = LDS_T > NTHREADS * 8 * 4 ? LDS_T : NTHREADS * 8 * 4;
     static_assert(LDS <= 160 * 1024, "wgrad tiles do not fit LDS");

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include "elt.h"
 #include "kernels.h"
 #include "../../include/vsrlab_hip.h"
 
@@ -26,23 +27,16 @@ constexpr int WQ = 16;                      // queries (pass 1) / keys (pass 2) 
 constexpr int MAXW = 8;                      // waves per workgroup: one (window, head) per workgroup, its query / key blocks shared by the waves
 constexpr int MAXT = 24;                    // score tiles of 16 per wave: N <= 384
 
-struct af8 { float v[8]; };
-template <typename T> struct AT;
-template <> struct AT<bf16_t> { typedef bf16x8_t frag_t; };
-template <> struct AT<float> { typedef af8 frag_t; };
-
 __device__ __forceinline__ void amma(f32x4_t& d, const bf16x8_t& a, const bf16x8_t& b) {
     d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, d, 0, 0, 0);
 }
-__device__ __forceinline__ void amma(f32x4_t& d, const af8& a, const af8& b) {
+__device__ __forceinline__ void amma(f32x4_t& d, const f32x8_t& a, const f32x8_t& b) {
     // slot j of lane group q is k = (q, j): any k order is valid as long as A and B agree
 #pragma unroll
     for (int j = 0; j < 8; ++j) d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], d, 0, 0, 0);
 }
 __device__ __forceinline__ void fset(bf16x8_t& f, int j, float v) { f[j] = (bf16_t)v; }
-__device__ __forceinline__ void fset(af8& f, int j, float v) { f.v[j] = v; }
-__device__ __forceinline__ float tof(bf16_t v) { return (float)v; }
-__device__ __forceinline__ float tof(float v) { return v; }
+__device__ __forceinline__ void fset(f32x8_t& f, int j, float v) { f.v[j] = v; }
 
 struct AttnArgs {
     const void* qkv;            // [B][N][3][nH][hd] of T
@@ -66,28 +60,24 @@ struct AttnArgs {
 };
 
 // 8 consecutive head-dim values [8q, 8q+8) of a token's q / k / v vector, zero beyond hd, times mul
-template <typename T> struct V4;
-template <> struct __attribute__((aligned(8))) V4<bf16_t> { bf16_t v[4]; };
-template <> struct __attribute__((aligned(16))) V4<float> { float v[4]; };
-
 template <typename T>
-__device__ __forceinline__ typename AT<T>::frag_t load_hd8(const T* p, int q, int hd, float mul) {
-    typename AT<T>::frag_t f;
+__device__ __forceinline__ typename Elt<T>::frag_t load_hd8(const T* p, int q, int hd, float mul) {
+    typename Elt<T>::frag_t f;
     if ((hd & 3) == 0) {                      // groups of 4 are all-valid or all-padding: two vector loads
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const int c0 = 8 * q + 4 * g;
-            V4<T> v;
-            if (c0 < hd) v = *reinterpret_cast<const V4<T>*>(p + c0);
+            Vec4<T> v;
+            if (c0 < hd) v = *reinterpret_cast<const Vec4<T>*>(p + c0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) fset(f, 4 * g + j, c0 < hd ? tof(v.v[j]) * mul : 0.f);
+            for (int j = 0; j < 4; ++j) fset(f, 4 * g + j, c0 < hd ? to_f(v.v[j]) * mul : 0.f);
         }
         return f;
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int c = 8 * q + j;
-        fset(f, j, c < hd ? tof(p[c]) * mul : 0.f);
+        fset(f, j, c < hd ? to_f(p[c]) * mul : 0.f);
     }
     return f;
 }
@@ -97,10 +87,10 @@ template <typename T>
 __device__ __forceinline__ void store_hd4(T* p, int c0, int hd, const f32x4_t& v, float mul) {
     if ((hd & 3) == 0) {
         if (c0 < hd) {
-            V4<T> o;
+            Vec4<T> o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o.v[j] = (T)(v[j] * mul);
-            *reinterpret_cast<V4<T>*>(p + c0) = o;
+            *reinterpret_cast<Vec4<T>*>(p + c0) = o;
         }
         return;
     }
@@ -117,11 +107,11 @@ __device__ __forceinline__ float xmax(float v) { v = fmaxf(v, __shfl_xor(v, 16, 
 // lds_k: [Nk][HP] of T (row-major keys).  st[t][j] = score(key 16 t + 4 q + j, query n).
 // ------------------------------------------------------------------------------------------------------------
 template <typename T, int NT>
-__device__ __forceinline__ void scores_T(const AttnArgs& a, const T* lds_k, const typename AT<T>::frag_t& qf, int b, int h, int qrow, int lane,
+__device__ __forceinline__ void scores_T(const AttnArgs& a, const T* lds_k, const typename Elt<T>::frag_t& qf, int b, int h, int qrow, int lane,
                                          f32x4_t (&st)[NT]) {
     constexpr int nt = NT;
     const int n = lane & 15, q = lane >> 4;
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
 #pragma unroll
     for (int t = 0; t < nt; ++t) {
         const frag_t kf = *reinterpret_cast<const frag_t*>(lds_k + (t * 16 + n) * HP + 8 * q);
@@ -167,7 +157,7 @@ __device__ __forceinline__ void stage_rows(const AttnArgs& a, int b, int h, int 
         for (int u = 0; u < 4; ++u) {
             const int idx = i0 + u * step;
             const int r = idx / HP, c = idx - r * HP;
-            v[u] = (idx < total && c < a.hd) ? tof(base[r * rs + c]) * mul : 0.f;
+            v[u] = (idx < total && c < a.hd) ? to_f(base[r * rs + c]) * mul : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -185,7 +175,7 @@ __device__ __forceinline__ void stage_rows(const AttnArgs& a, int b, int h, int 
 template <typename T, int NT>
 __global__ __launch_bounds__(MAXW * 64) void attn_fwd_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     T* lds_k = reinterpret_cast<T*>(smem);                  // [Nk][HP]
     T* lds_vt = lds_k + a.Nk * HP;                          // [HP][tstride(Nk)]
     const int b = blockIdx.z, h = blockIdx.y;
@@ -226,7 +216,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_kernel(const AttnArgs a) {
             const T* vp = lds_vt + (mb * 16 + n) * vts + 32 * s + 4 * q;
             frag_t vf;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { fset(vf, j, tof(vp[j])); fset(vf, 4 + j, tof(vp[16 + j])); }
+            for (int j = 0; j < 4; ++j) { fset(vf, j, to_f(vp[j])); fset(vf, 4 + j, to_f(vp[16 + j])); }
             amma(o[mb], vf, pf);
         }
     }
@@ -246,7 +236,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_fwd_kernel(const AttnArgs a) {
 template <typename T, int NT>
 __global__ __launch_bounds__(MAXW * 64) void attn_bwd_q_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     T* lds_k = reinterpret_cast<T*>(smem);                  // [Nk][HP]
     T* lds_v = lds_k + a.Nk * HP;                           // [Nk][HP]
     T* lds_kt = lds_v + a.Nk * HP;                          // [HP][tstride(Nk)]
@@ -304,7 +294,7 @@ __global__ __launch_bounds__(MAXW * 64) void attn_bwd_q_kernel(const AttnArgs a)
             const T* kp = lds_kt + (mb * 16 + n) * kts + 32 * s + 4 * q;
             frag_t kf;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { fset(kf, j, tof(kp[j])); fset(kf, 4 + j, tof(kp[16 + j])); }
+            for (int j = 0; j < 4; ++j) { fset(kf, j, to_f(kp[j])); fset(kf, 4 + j, to_f(kp[16 + j])); }
             amma(dq[mb], kf, sf);
         }
     }
@@ -327,7 +317,7 @@ inline int kv_chunk(int Nq) { return Nq <= QC ? Nq : (Nq % QC == 0 ? QC : (Nq % 
 template <typename T>
 __global__ __launch_bounds__(MAXW * 64) void attn_bwd_kv_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     const int qc = a.qc;
     T* lds_q = reinterpret_cast<T*>(smem);                  // [qc][HP]   (q * scale)
     T* lds_do = lds_q + qc * HP;                            // [qc][HP]
@@ -408,8 +398,8 @@ __global__ __launch_bounds__(MAXW * 64) void attn_bwd_kv_kernel(const AttnArgs a
                 frag_t df, qtf;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    fset(df, j, tof(dop[j])); fset(df, 4 + j, tof(dop[16 + j]));
-                    fset(qtf, j, tof(qtp[j])); fset(qtf, 4 + j, tof(qtp[16 + j]));
+                    fset(df, j, to_f(dop[j])); fset(df, 4 + j, to_f(dop[16 + j]));
+                    fset(qtf, j, to_f(qtp[j])); fset(qtf, 4 + j, to_f(qtp[16 + j]));
                 }
                 amma(dv[mb], df, pf);                       // dV^T[hd][key] += dO^T[hd][queries] P[queries][key]
                 amma(dk[mb], qtf, sf);                      // dK^T[hd][key] += (scale Q)^T[hd][queries] dS[queries][key]
@@ -512,7 +502,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attn_fwd_p_kernel(const AttnA
     constexpr int NK = NT * 16, NTH = NW * 64, TS = NK + 8;
     constexpr int BUF = NK * HP + HP * TS;                   // elements per buffer: K [NK][HP] + V^T [HP][TS]
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     T* lds = reinterpret_cast<T*>(smem);
     const PWalk w = pwalk(a);
     const int h = w.h, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, q = lane >> 4;
@@ -578,7 +568,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attn_fwd_p_kernel(const AttnA
                 const T* vp = lds_vt + (mb * 16 + n) * TS + 32 * s + 4 * q;
                 frag_t vf;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { fset(vf, j, tof(vp[j])); fset(vf, 4 + j, tof(vp[16 + j])); }
+                for (int j = 0; j < 4; ++j) { fset(vf, j, to_f(vp[j])); fset(vf, 4 + j, to_f(vp[16 + j])); }
                 amma(o[mb], vf, pf);
             }
         }
@@ -599,7 +589,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_q_p_kernel(const AttnArgs a)
     constexpr int NK = NT * 16, NTH = NW * 64, TS = NK + 8;
     constexpr int BUF = 2 * NK * HP + HP * TS;               // K [NK][HP], V [NK][HP], K^T [HP][TS]
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     T* lds = reinterpret_cast<T*>(smem);
     const PWalk w = pwalk(a);
     const int h = w.h, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, q = lane >> 4;
@@ -675,7 +665,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_q_p_kernel(const AttnArgs a)
                 const T* kp = lds_kt + (mb * 16 + n) * TS + 32 * s + 4 * q;
                 frag_t kf;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { fset(kf, j, tof(kp[j])); fset(kf, 4 + j, tof(kp[16 + j])); }
+                for (int j = 0; j < 4; ++j) { fset(kf, j, to_f(kp[j])); fset(kf, 4 + j, to_f(kp[16 + j])); }
                 amma(dq[mb], kf, sf);
             }
         }
@@ -703,7 +693,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kv_p_kernel(const AttnArgs a
     constexpr int NQ = NQT * 16, NTH = NW * 64, TS = NQ + 8;
     constexpr int BUF = 2 * NQ * HP + 2 * HP * TS;           // Q [NQ][HP], dO [NQ][HP], Q^T [HP][TS], dO^T [HP][TS]
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename AT<T>::frag_t frag_t;
+    typedef typename Elt<T>::frag_t frag_t;
     T* lds = reinterpret_cast<T*>(smem);
     float* lds_f = reinterpret_cast<float*>(lds + 2 * BUF);  // [2][2][NQ]: lse, delta per buffer
     const PWalk w = pwalk(a);
@@ -777,8 +767,8 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kv_p_kernel(const AttnArgs a
                 frag_t df, qtf;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    fset(df, j, tof(dop[j])); fset(df, 4 + j, tof(dop[16 + j]));
-                    fset(qtf, j, tof(qtp[j])); fset(qtf, 4 + j, tof(qtp[16 + j]));
+                    fset(df, j, to_f(dop[j])); fset(df, 4 + j, to_f(dop[16 + j]));
+                    fset(qtf, j, to_f(qtp[j])); fset(qtf, 4 + j, to_f(qtp[16 + j]));
                 }
                 amma(dv[mb], df, pf);
                 amma(dk[mb], qtf, sf);

@@ -411,6 +411,35 @@ size_t vsr_metrics_scratch_bytes(const VsrMetricsDesc* d);       /* 0: unsupport
 int vsr_psnr_ssim(const VsrMetricsDesc* d, const float* x, const float* y, double* sums, void* scratch, size_t scratch_bytes,
                   void* stream);
 
+/* ---- RAFT's correlation lookup without the all-pairs volume (csrc/raft_corr.hip) -----------------------
+ * optical_flow/models/raft/corr.py: out[n][l*49 + i*7 + j][p] = bilinear sample, zeros outside, of level l of
+ * corr[p][q] = <fmap1[p], fmap2[q]> / float32(sqrt(D)) at (x, y) = coords[p] / 2^l + (i - 3, j - 3): window index i (slow)
+ * offsets x and j (fast) offsets y, as the reference's meshgrid does.  Level l of the volume equals the dot products with
+ * fmap2 pooled l times by avg_pool2d(2, 2) (floor sizes), which is what is stored: nothing of size (H*W)^2 exists.
+ *   fmap1, fmap2 (N,D,H,W), coords (N,2,H,W) channel 0 = x, out / dout (N, levels*49, H, W): fp32 planar.
+ *   packed: workspace_bytes(d, 0) bytes; pyramid_fwd fills it (pixel-major fmap1 and levels in `dtype`, pooled in fp32);
+ *           any number of lookup_fwd / lookup_bwd calls then read it.
+ *   gacc:   workspace_bytes(d, 1) bytes of fp32 gradient accumulators, zeroed by the caller; every lookup_bwd ADDS its
+ *           d fmap1 (gather, one owner per element: bit-identical across runs) and d level (fp32 atomic adds: reproducible
+ *           to rounding); pyramid_bwd un-pools the levels inside gacc (it is consumed) and writes planar dfmap1 / dfmap2
+ *           (either may be NULL).  coords receive no gradient.
+ * Coordinates are clamped in float before any integer conversion: huge or non-finite ones give windows of exact zeros.
+ * Supported: D = 128, radius 3, 1..4 levels, every level at least 2 x 2 (the reference divides by W_l - 1), H*W <= 2^24,
+ * N*H*W <= 2^28, N <= 65535; anything else is VSR_STATUS_UNSUPPORTED (workspace_bytes: 0).                              */
+typedef struct VsrRaftCorrDesc {
+    int N, D, H, W;
+    int levels, radius;
+    int dtype;
+} VsrRaftCorrDesc;
+size_t vsr_raft_corr_workspace_bytes(const VsrRaftCorrDesc* d, int gradients);          /* 0: unsupported descriptor */
+int vsr_raft_corr_pyramid_fwd(const VsrRaftCorrDesc* d, const float* fmap1, const float* fmap2, void* packed, size_t packed_bytes,
+                              void* stream);
+int vsr_raft_corr_pyramid_bwd(const VsrRaftCorrDesc* d, void* gacc, size_t gacc_bytes, float* dfmap1, float* dfmap2, void* stream);
+int vsr_raft_corr_lookup_fwd(const VsrRaftCorrDesc* d, const void* packed, size_t packed_bytes, const float* coords, float* out,
+                             void* stream);
+int vsr_raft_corr_lookup_bwd(const VsrRaftCorrDesc* d, const void* packed, size_t packed_bytes, const float* coords, const float* dout,
+                             void* gacc, size_t gacc_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

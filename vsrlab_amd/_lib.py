@@ -49,6 +49,11 @@ class MetricsDesc(ctypes.Structure):
                 ("sigma", c_float), ("c1", c_float), ("c2", c_float), ("clamp_x", c_int), ("clamp_lo", c_float), ("clamp_hi", c_float)]
 
 
+class RaftCorrDesc(ctypes.Structure):
+    """struct VsrRaftCorrDesc (include/vsrlab_hip.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "D", "H", "W", "levels", "radius", "dtype")]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -115,6 +120,11 @@ _SIGNATURES = {
     "vsr_deform_offset_mask": (c_int, [ctypes.POINTER(DeformDesc), _P, _P, _P, _P, _P]),
     "vsr_metrics_scratch_bytes": (c_size_t, [ctypes.POINTER(MetricsDesc)]),
     "vsr_psnr_ssim": (c_int, [ctypes.POINTER(MetricsDesc), _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_raft_corr_workspace_bytes": (c_size_t, [ctypes.POINTER(RaftCorrDesc), c_int]),
+    "vsr_raft_corr_pyramid_fwd": (c_int, [ctypes.POINTER(RaftCorrDesc), _P, _P, _P, c_size_t, _P]),
+    "vsr_raft_corr_pyramid_bwd": (c_int, [ctypes.POINTER(RaftCorrDesc), _P, c_size_t, _P, _P, _P]),
+    "vsr_raft_corr_lookup_fwd": (c_int, [ctypes.POINTER(RaftCorrDesc), _P, c_size_t, _P, _P, _P]),
+    "vsr_raft_corr_lookup_bwd": (c_int, [ctypes.POINTER(RaftCorrDesc), _P, c_size_t, _P, _P, _P, c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

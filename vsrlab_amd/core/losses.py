@@ -1,11 +1,14 @@
 """``CharbonnierLoss`` (vsrlab ``src/core/losses.py:10-18``), fused value+gradient HIP kernel; ``AdversarialLoss``;
-``PerceptualLoss`` (VGG19, ``src/core/losses.py:29-64``) on the HIP perceptual engine."""
+``PerceptualLoss`` (VGG19, ``src/core/losses.py:29-64``) on the HIP perceptual engine; ``OpticalFlowConsistency`` (RAFT-small,
+``src/core/losses.py:79-98``) on the fused HIP correlation lookup."""
 import os
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import functional as VF
+from ..optical_flow.models.raft.raft import RAFT
 
 
 class CharbonnierLoss(nn.Module):
@@ -101,3 +104,25 @@ class PerceptualLoss(nn.Module):
 
     def forward(self, yhat, y):
         return VF.perceptual_loss(yhat, y, self.vgg.params(), self.weight, max_workspace_bytes=self.max_workspace_bytes)
+
+
+class OpticalFlowConsistency(nn.Module):
+    """``OpticalFlowConsistency`` (``src/core/losses.py:79-98``): ``weight * l1(flow(sr), flow(hr))`` of frozen RAFT-small
+    (``scale_factor=8``) between consecutive frames of (B, T, C, H, W) clips.  ``weights``: path or state dict; None = the
+    checkpoint under ``$PROJECT_ROOT`` (``FileNotFoundError`` if absent: nothing is downloaded).  ``compute_dtype``: storage of
+    the correlation pyramid.  The HR flow needs no gradient and is computed under ``no_grad`` (same values); the SR flow
+    differentiates into ``sr``.  H and W: multiples of 8, at least 128."""
+
+    def __init__(self, weight=1.0, weights=None, compute_dtype=None):
+        super().__init__()
+        self.of = RAFT(small=True, scale_factor=8, pretrained=True, weights=weights, compute_dtype=compute_dtype)
+        self.weight = weight
+        for p in self.of.parameters():
+            p.requires_grad = False
+
+    def forward(self, sr, hr):
+        b, t, c, h, w = sr.shape
+        flow_sr = self.of(sr[:, 1:].reshape(-1, c, h, w), sr[:, :-1].reshape(-1, c, h, w))
+        with torch.no_grad():
+            flow_hr = self.of(hr[:, 1:].reshape(-1, c, h, w), hr[:, :-1].reshape(-1, c, h, w))
+        return F.l1_loss(flow_sr, flow_hr) * self.weight

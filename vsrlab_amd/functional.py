@@ -1449,3 +1449,151 @@ def psnr_ssim(x: torch.Tensor, y: torch.Tensor, *, window_size: int = 11, sigma:
     _lib.check(lib.vsr_psnr_ssim(ctypes.byref(desc), _ptr(x4), _ptr(y4), _ptr(sums), _ptr(scratch), nbytes, _stream()), "psnr_ssim")
     return PsnrSsimSums(mse=sums[:, 1] / float(c * h * w), ssim=sums[:, 0] / float(c * (h - ws + 1) * (w - ws + 1)),
                         sq_err_sum=sums[:, 1], ss_sum=sums[:, 0])
+
+
+# --------------------------------------------------------------------------------------------- #
+# RAFT's correlation lookup without the all-pairs volume
+# (reference: optical_flow/models/raft/corr.py; csrc/raft_corr.hip)
+# --------------------------------------------------------------------------------------------- #
+_RAFT_UNSUPPORTED = ("vsrlab_amd: raft_corr: unsupported shape (D = 128, radius 3, 1..4 levels, every pooled level at least "
+                     "2 x 2): fmap {shape}, num_levels {levels}, radius {radius}")
+
+
+def raft_corr_workspace_bytes(fmap_shape, num_levels: int = 4, radius: int = 3, dtype: int = DT_F32, gradients: bool = False) -> int:
+    """Bytes of the packed maps of one pyramid (``gradients=False``) or of its fp32 gradient accumulators; 0: unsupported
+    shape.  Host arithmetic only."""
+    n, d, h, w = fmap_shape
+    desc = _lib.RaftCorrDesc(int(n), int(d), int(h), int(w), int(num_levels), int(radius), int(dtype))
+    return int(_lib.load().vsr_raft_corr_workspace_bytes(ctypes.byref(desc), int(bool(gradients))))
+
+
+class _RaftCorrState:
+    """Device state of one pyramid, shared by the autograd nodes of the pyramid and of its lookups (it does not refer to them:
+    no reference cycle through the graph)."""
+
+    def __init__(self, desc, packed, shape, num_levels, need_bwd):
+        self.desc, self.packed, self.shape, self.num_levels, self.need_bwd = desc, packed, tuple(shape), num_levels, need_bwd
+        self.gacc = None                        # fp32 gradient accumulators, allocated by the first lookup backward
+
+
+class RaftCorrPyramid:
+    """What ``raft_corr_pyramid`` returns: the packed fmap1 and the pooled levels of fmap2 on the device, for any number of
+    ``raft_corr_lookup`` calls.  The gradients of all those lookups are summed in fp32 accumulators and leave through the
+    pyramid's own backward, once (``token`` is what ties the lookups to it in the autograd graph)."""
+
+    def __init__(self, state, token):
+        self.state, self.token = state, token
+        self.shape, self.num_levels = state.shape, state.num_levels
+
+    @property
+    def out_channels(self):
+        return self.num_levels * 49
+
+    @property
+    def packed_bytes(self):
+        return self.state.packed.numel()
+
+
+class _RaftPyramidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, handle):
+        f1, f2 = _f32c(fmap1), _f32c(fmap2)
+        _lib.check(_lib.load().vsr_raft_corr_pyramid_fwd(ctypes.byref(handle.desc), _ptr(f1), _ptr(f2), _ptr(handle.packed),
+                                                         handle.packed.numel(), _stream()), "raft_corr_pyramid_fwd")
+        ctx.handle = handle
+        ctx.dtypes = (fmap1.dtype, fmap2.dtype)
+        ctx.backward_done = False
+        return torch.zeros(1, dtype=torch.float32, device=f1.device)
+
+    @staticmethod
+    def backward(ctx, gtoken):
+        if torch.is_grad_enabled():
+            raise RuntimeError("vsrlab_amd: raft_corr_pyramid has no double backward (create_graph=True is not supported)")
+        if ctx.backward_done:
+            raise RuntimeError("vsrlab_amd: trying to backward through raft_corr_pyramid a second time")
+        ctx.backward_done = True
+        h = ctx.handle
+        gacc, h.gacc = h.gacc, None
+        if gacc is None:                        # no lookup of this pyramid was differentiated
+            return None, None, None
+        need = ctx.needs_input_grad
+        dev = gacc.device
+        d1 = torch.empty(h.shape, dtype=torch.float32, device=dev) if need[0] else None
+        d2 = torch.empty(h.shape, dtype=torch.float32, device=dev) if need[1] else None
+        _lib.check(_lib.load().vsr_raft_corr_pyramid_bwd(ctypes.byref(h.desc), _ptr(gacc), gacc.numel(), _ptr(d1), _ptr(d2), _stream()),
+                   "raft_corr_pyramid_bwd")
+        del gacc
+        return (None if d1 is None else d1.to(ctx.dtypes[0]), None if d2 is None else d2.to(ctx.dtypes[1]), None)
+
+
+class _RaftLookupFn(torch.autograd.Function):
+    """out = the 7 x 7 windows of every level at ``coords``.  The backward adds into the pyramid's accumulators: d fmap1 is
+    bit-identical across runs, d fmap2 is summed with fp32 atomic adds (reproducible to rounding).  ``coords`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, token, coords, handle):
+        n, _, h, w = handle.shape
+        c32 = _f32c(coords)
+        out = torch.empty((n, handle.num_levels * 49, h, w), dtype=torch.float32, device=c32.device)
+        _lib.check(_lib.load().vsr_raft_corr_lookup_fwd(ctypes.byref(handle.desc), _ptr(handle.packed), handle.packed.numel(), _ptr(c32),
+                                                        _ptr(out), _stream()), "raft_corr_lookup_fwd")
+        ctx.handle = handle
+        ctx.coords = c32 if handle.need_bwd else None
+        ctx.backward_done = False
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if torch.is_grad_enabled():
+            raise RuntimeError("vsrlab_amd: raft_corr_lookup has no double backward (create_graph=True is not supported)")
+        if ctx.backward_done:
+            raise RuntimeError("vsrlab_amd: trying to backward through raft_corr_lookup a second time")
+        if ctx.coords is None:
+            raise RuntimeError("vsrlab_amd: backward through a raft_corr_lookup that ran without a gradient")
+        lib = _lib.load()
+        h = ctx.handle
+        c32, ctx.coords, ctx.backward_done = ctx.coords, None, True
+        gout = _f32c(gout)
+        if h.gacc is None:
+            nbytes = int(lib.vsr_raft_corr_workspace_bytes(ctypes.byref(h.desc), 1))
+            h.gacc = torch.zeros(nbytes, dtype=torch.uint8, device=gout.device)
+        _lib.check(lib.vsr_raft_corr_lookup_bwd(ctypes.byref(h.desc), _ptr(h.packed), h.packed.numel(), _ptr(c32), _ptr(gout),
+                                                _ptr(h.gacc), h.gacc.numel(), _stream()), "raft_corr_lookup_bwd")
+        return torch.zeros(1, dtype=torch.float32, device=gout.device), None, None
+
+
+def raft_corr_pyramid(fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, compute_dtype: Optional[str] = None,
+                      radius: int = 3) -> RaftCorrPyramid:
+    """Pack ``fmap1`` and build the ``avg_pool2d(2, 2)`` pyramid of ``fmap2`` (both (N, 128, H, W)) once; the returned handle
+    serves every ``raft_corr_lookup`` of a forward pass.  Storage is fp32, or bf16 under ``compute_dtype='bf16'`` (fp32
+    accumulation either way).  Nothing of size (H W)^2 is ever formed."""
+    if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
+        raise ValueError(f"raft_corr_pyramid: fmap1 and fmap2 must have one shape (N, D, H, W); got {tuple(fmap1.shape)} and {tuple(fmap2.shape)}")
+    _require_gpu(fmap1, fmap2)
+    dtype = resolve_dtype(compute_dtype)
+    n, d, h, w = (int(v) for v in fmap1.shape)
+    desc = _lib.RaftCorrDesc(n, d, h, w, int(num_levels), int(radius), dtype)
+    nbytes = int(_lib.load().vsr_raft_corr_workspace_bytes(ctypes.byref(desc), 0))
+    if nbytes == 0:
+        raise RuntimeError(_RAFT_UNSUPPORTED.format(shape=tuple(fmap1.shape), levels=num_levels, radius=radius))
+    need_bwd = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
+    state = _RaftCorrState(desc, torch.empty(nbytes, dtype=torch.uint8, device=fmap1.device), fmap1.shape, int(num_levels), need_bwd)
+    return RaftCorrPyramid(state, _RaftPyramidFn.apply(fmap1, fmap2, state))
+
+
+def raft_corr_lookup(handle: RaftCorrPyramid, coords: torch.Tensor) -> torch.Tensor:
+    """(N, num_levels * 49, H, W): channel ``l * 49 + i * 7 + j`` is level ``l`` of the correlation of every pixel with the
+    pyramid, sampled bilinearly (zeros outside) at ``coords / 2^l + (i - 3, j - 3)`` -- ``i`` offsets x and ``j`` offsets y, as
+    the reference's meshgrid does.  ``coords`` is (N, 2, H, W) with channel 0 = x and receives no gradient; the result is
+    differentiable into both maps of the pyramid."""
+    n, _, h, w = handle.shape
+    if tuple(coords.shape) != (n, 2, h, w):
+        raise ValueError(f"raft_corr_lookup: coords must be ({n}, 2, {h}, {w}); got {tuple(coords.shape)}")
+    _require_gpu(coords)
+    return _RaftLookupFn.apply(handle.token, coords.detach(), handle.state)
+
+
+def raft_correlation(coords: torch.Tensor, fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, radius: int = 3,
+                     compute_dtype: Optional[str] = None) -> torch.Tensor:
+    """The reference's ``correlation(coords, fmap1, fmap2, num_levels, radius)`` in one call: pyramid + one lookup."""
+    return raft_corr_lookup(raft_corr_pyramid(fmap1, fmap2, num_levels, compute_dtype, radius=radius), coords)

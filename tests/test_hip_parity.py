@@ -1333,3 +1333,77 @@ def test_spynet_7x7_weight_gradients_on_the_producer_consumer_kernel(shape):
             assert rel_l2(a, r) < 1e-2, (shape, ci, co, name, rel_l2(a, r))
         again = run(lambda x, wt, b: VF.conv_relu_forward(x, wt, b, compute_dtype="bf16"))
         assert all(torch.equal(a, b) for a, b in zip(got, again)), (shape, ci, co)
+
+
+# --------------------------------------------------------------------------------------------- #
+# The reconstruction tail end to end at a ragged size (13 x 37: HR 52 x 148 / 26 x 74 -- partial 8-row tiles and partial 32-pixel
+# segments at every resolution), bf16 build with backward; the kernels one by one: tests/test_hr_tail_gpu.py.
+def _ragged_tail_run(upscale, dev, shape=(1, 2, 3, 13, 37)):
+    from vsrlab_amd.vsr.models.RealBasicVSR.modules.basicvsr import BasicVSR
+    n, t, _, h, w = shape
+    sd = O.keyed_state_dict(O.basicvsr_param_shapes(64, 2, upscale))
+    if upscale == 4:
+        m, lrs, cot, sr, grads = _run_basicvsr("bf16", 64, 2, shape, 81, 82, dev)
+    else:
+        m = BasicVSR(64, 2, upscale, False, False)
+        m.load_state_dict(sd, strict=True)
+        m = m.to(dev)
+        m.compute_dtype = "bf16"
+        lrs, cot = rand(81, *shape), rand(82, n, t, 3, upscale * h, upscale * w, lo=-1, hi=1)
+        sr = m(lrs.to(dev))
+        torch.mean(sr * cot.to(dev)).backward()
+        grads = {k: p.grad.detach().cpu() for k, p in m.named_parameters() if p.grad is not None}
+        sr = sr.detach().cpu()
+    sr_x, _, g_x = O.fwd_bwd({k: v.double() for k, v in sd.items()}, lrs.double(), cot.double(), cot=cot.double())
+    with O.emulate_bf16():
+        sr_e, _, g_e = O.fwd_bwd(sd, lrs, cot, cot=cot)
+    assert tuple(sr.shape) == (n, t, 3, upscale * h, upscale * w) and set(grads) == set(g_x)
+    assert rel_err(sr, sr_x) <= 1.5 * max(rel_err(sr_e, sr_x), 1e-3), (rel_err(sr, sr_x), rel_err(sr_e, sr_x))
+    return _noise_floor_check(grads, g_e, g_x, max_glob_ratio=1.5, max_tensor_ratio=2.5)
+
+
+def test_ragged_reconstruction_tail_upscale_4_bf16():
+    """BasicVSR(64, 2) upscale 4 at (1,2,3,13,37) with backward: HR 52 x 148 (W % 4 == 0: the ring weight-gradient kernel, 6.5 tile rows,
+    a 20-pixel last segment), the phase-separated pixel-shuffle gradients at 13 x 37 and 26 x 74.  fp64 oracle and its bf16 emulation:
+    1.5 x globally, 2.5 x per tensor."""
+    _ragged_tail_run(4, _gpu())
+
+
+def test_ragged_reconstruction_tail_upscale_2_takes_the_plain_wgrad_kernel_bf16():
+    """The same net with upscale 2: HR 26 x 74, and 74 % 4 != 0, so conv_last.2's weight gradient runs on last2_wgrad_kernel (every other
+    bf16 backward of the suite has an HR width divisible by 4 and takes the ring kernel)."""
+    _ragged_tail_run(2, _gpu())
+
+
+def test_ragged_preclean_stack_bf16():
+    """RealBasicVSR (2 cleaning blocks, 2 residual blocks) at (1,1,3,13,37) with backward: the pre-clean stack's planar stem, its 64 -> 3
+    out conv with the planar residual, their data and weight gradients at 13 x 37 (37 % 4 != 0: the plain weight-gradient kernel),
+    three iterations sharing their weights; t = 1 has no flow path.  Criteria as test_realbasicvsr_training_vs_oracle."""
+    from helpers import realbasicvsr_shapes, realbasicvsr_oracle_grads
+    from vsrlab_amd.vsr.models.RealBasicVSR.realbasicvsr import RealBasicVSR
+    dev = _gpu()
+    sd32 = O.keyed_state_dict(realbasicvsr_shapes(64, 2, 2))
+    m = RealBasicVSR(2, mid_channels=64, upscale=4, res_blocks=2, pretrained_flow=False, train_flow=False)
+    m.load_state_dict(sd32, strict=True)
+    m = m.to(dev)
+    m.basicvsr.compute_dtype = "bf16"
+    shape = (1, 1, 3, 13, 37)
+    n, t, _, h, w = shape
+    lr, cot_sr, cot_lq = rand(84, *shape), rand(85, n, t, 3, 4 * h, 4 * w, lo=-1, hi=1), rand(86, n, t, 3, h, w, lo=-1, hi=1)
+    os.environ["VSRLAB_AMD_DTYPE"] = "bf16"
+    try:
+        sr, lq = m(lr.clone().to(dev))
+        (torch.mean(sr * cot_sr.to(dev)) + torch.mean(lq * cot_lq.to(dev))).backward()
+    finally:
+        del os.environ["VSRLAB_AMD_DTYPE"]
+    sr_o, lq_o, ref = realbasicvsr_oracle_grads({k: v.double() for k, v in sd32.items()}, lr.double(), cot_sr.double(), cot_lq.double())
+    with O.emulate_bf16():
+        sr_e, lq_e, g_e = realbasicvsr_oracle_grads(sd32, lr, cot_sr, cot_lq)
+    grads = {k: p.grad.detach().cpu() for k, p in m.named_parameters() if p.grad is not None}
+    assert set(grads) == set(ref)
+    cl = {k: v for k, v in ref.items() if k.startswith("cleaner.")}
+    assert len(cl) == 12
+    assert rel_err(lq, lq_o) <= 1.5 * max(rel_err(lq_e, lq_o), 1e-3), (rel_err(lq, lq_o), rel_err(lq_e, lq_o))
+    assert rel_err(sr, sr_o) <= 1.5 * max(rel_err(sr_e, sr_o), 1e-3), (rel_err(sr, sr_o), rel_err(sr_e, sr_o))
+    _noise_floor_check(grads, g_e, ref, max_glob_ratio=1.5, max_tensor_ratio=2.5)
+    _noise_floor_check({k: grads[k] for k in cl}, {k: g_e[k] for k in cl}, cl, max_glob_ratio=1.5, max_tensor_ratio=2.5)

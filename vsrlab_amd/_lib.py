@@ -128,6 +128,24 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
+# Test hooks of csrc/hr_tail_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in EXPORTS, like the other
+# vsr_debug_* entries, whose argument types the tests that call them set by hand).  These seven have long mixed int / long long /
+# float / pointer lists and three callers (both hr_tail tests, the driver), so their types are stated once, here; load() applies them.
+# OTHER_DEBUG_EXPORTS: the library's remaining vsr_debug_* symbols.  EXPORTS + OTHER_DEBUG_EXPORTS + DEBUG_SIGNATURES is every
+# `vsr_` symbol the product library exports (tests/test_hr_tail_host.py enumerates its dynamic symbol table against this).
+OTHER_DEBUG_EXPORTS = ("vsr_debug_chain_inject_error", "vsr_debug_chain_item", "vsr_debug_chain_timeouts", "vsr_debug_chain_timing_begin",
+                       "vsr_debug_chain_timing_read", "vsr_debug_warp_bwd_gather", "vsr_debug_warp_bwd_gather_c")
+_LL = c_longlong
+DEBUG_SIGNATURES = {
+    "vsr_debug_tail_last2_fwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _LL, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_last2_dgrad": (c_int, [_P, _LL, _P, _P, c_int, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_planar_c64": (c_int, [c_int, _P, _LL, c_int, _P, _P, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_last2_wgrad": (c_int, [c_int, _P, _P, _LL, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_conv_unshuffle": (c_int, [c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_ps_dgrad": (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_tail_ps_wgrads": (c_int, [c_int, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -144,6 +162,13 @@ def load():
             fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args) in DEBUG_SIGNATURES.items():
+            # the project's own build must have them (AttributeError, as for the ABI above); only a library named by
+            # VSRLAB_AMD_LIB, e.g. a parent commit's for an A/B run, may predate them
+            fn = getattr(lib, name, None) if os.environ.get("VSRLAB_AMD_LIB") else getattr(lib, name)
+            if fn is not None:
+                fn.restype = res
+                fn.argtypes = args
         _lib = lib
     return _lib
 

@@ -66,7 +66,9 @@ inline int wgrad_launch(hipStream_t st, int dtype, float* slab, WgradArgs& a, co
     if (dtype == VSR_BF16 && s.ks == 3 && s.cx == 64 && !s.x_planar && s.cout == 16 && s.dy_planar && a.nseg == 1 && a.x_step == 1 &&
         a.dy_step == 1 && a.Hx == a.H && a.Wx == a.W && a.Hy == a.H && a.Wy == a.W)
         // 64 -> 3 conv with a planar cotangent (conv_last.2, the pre-clean out conv): streaming kernel of hr_tail.hip
-        return vsr_launch_last2_wgrad(a.x[0], reinterpret_cast<const float*>(a.dy[0]), a.dy_nstride, slab, stride, a.N, a.H, a.W, nslabs, st);
+        // (pc: a cotangent of 1 or 2 planes has no plane 2 to read -- the launcher's default of 3 read past it)
+        return vsr_launch_last2_wgrad(a.x[0], reinterpret_cast<const float*>(a.dy[0]), a.dy_nstride, slab, stride, a.N, a.H, a.W, nslabs, st,
+                                      a.dy_planar_c ? a.dy_planar_c : 3);
     return vsr_launch_wgrad(dtype, s.ks, s.cx, s.x_planar, s.cout, s.dy_planar, a, nwg, nslabs, st);
 }
 // ... + its reduction into d.gw / d.gb (neither wanted: nothing is launched; a bias gradient needs its weight's)

@@ -64,14 +64,14 @@ def draw(seed, *shape):
     return bf16_round(torch.rand(*shape, generator=g) * 2 - 1)
 
 
-def draw_aux(seed, n, h, w):
-    """An activation (N, 64, H, W): bf16-representable values of both signs with +0.0, -0.0 and +-2^-133 at every pixel's channels
+def draw_aux(seed, n, h, w, c=64):
+    """An activation (N, c, H, W): bf16-representable values of both signs with +0.0, -0.0 and +-2^-133 at every pixel's channels
     0..3 of the first and the last column and sprinkled over ~3 % of the rest."""
-    a = draw(seed, n, 64, h, w)
+    a = draw(seed, n, c, h, w)
     g = torch.Generator().manual_seed(int(seed) + 1)
-    pick = torch.rand(n, 64, h, w, generator=g)
+    pick = torch.rand(n, c, h, w, generator=g)
     special = torch.tensor([0.0, -0.0, SUBNORMAL, -SUBNORMAL])
-    kind = torch.randint(0, 4, (n, 64, h, w), generator=g)
+    kind = torch.randint(0, 4, (n, c, h, w), generator=g)
     a = torch.where(pick < 0.03, special[kind], a)
     for col in (0, w - 1):
         a[:, 0:4, :, col] = special.view(1, 4, 1)
@@ -363,11 +363,15 @@ def bounds(c: Case):
 def measure(c: Case, got):
     """dict name -> (worst err / bound, worst (err - rounding terms) / accumulation term, index of the worst element).  An element whose
     bound is 0 has to be exact (ratio 0 or inf).  NaN anywhere in `got` gives inf."""
-    r, _, _ = reference(c)
+    return measure_against(c.name, got, reference(c)[0], bounds(c))
+
+
+def measure_against(name, got, r, bnds):
+    """measure() on explicit references: r[k] the fp64 values, bnds[k] = (accumulation term, rounding terms) (tests/trunk_common.py too)."""
     res = {}
-    for k, (acc, rnd) in bounds(c).items():
+    for k, (acc, rnd) in bnds.items():
         g = got[k].double()
-        assert g.shape == r[k].shape, (c.name, k, tuple(g.shape), tuple(r[k].shape))
+        assert g.shape == r[k].shape, (name, k, tuple(g.shape), tuple(r[k].shape))
         err = (g - r[k]).abs()
         err = torch.where(torch.isfinite(g), err, torch.full_like(err, float("inf")))
         b = acc + rnd
@@ -381,9 +385,12 @@ def measure(c: Case, got):
 
 def describe_failures(c: Case, got, limit=6):
     """Which elements are outside their bound: per output the count and the first few (index, got, reference, bound)."""
-    r, _, _ = reference(c)
+    return describe_failures_against(got, reference(c)[0], bounds(c), limit)
+
+
+def describe_failures_against(got, r, bnds, limit=6):
     lines = []
-    for k, (acc, rnd) in bounds(c).items():
+    for k, (acc, rnd) in bnds.items():
         g = got[k].double()
         bad = ~((g - r[k]).abs() <= acc + rnd)
         idx = bad.nonzero()
@@ -395,11 +402,15 @@ def describe_failures(c: Case, got, limit=6):
 
 def check(c: Case, got, label="hip"):
     """Every element of every output inside its bound; prints the worst ratios; returns measure()'s dict."""
-    m = measure(c, got)
+    return check_against(c.name, got, reference(c)[0], bounds(c), label)
+
+
+def check_against(name, got, r, bnds, label="hip", tag="HR_TAIL_RATIO"):
+    m = measure_against(name, got, r, bnds)
     for k, (ratio, acc_ratio, idx) in m.items():
-        print(f"HR_TAIL_RATIO {label} {c.name} {k}: worst err/bound {ratio:.3f} at {idx}, accumulation share {acc_ratio:.3f}")
+        print(f"{tag} {label} {name} {k}: worst err/bound {ratio:.3f} at {idx}, accumulation share {acc_ratio:.3f}")
     bad = {k: v for k, v in m.items() if not v[0] <= 1.0}
-    assert not bad, (c.name, describe_failures(c, got))
+    assert not bad, (name, describe_failures_against(got, r, bnds))
     return m
 
 
@@ -461,9 +472,9 @@ class Planar:
 
 
 def pm_input(t, dtype, dev):
-    """(N, 64, H, W) CPU fp32 -> the blocked pixel-major tensor in a NaN-banded buffer, padding pixels NaN."""
+    """(N, C, H, W) CPU fp32, C = 16, 32 or 64 -> the blocked pixel-major tensor in a NaN-banded buffer, padding pixels NaN."""
     from vsrlab_amd import functional as VF
-    pm = VF.to_pixel_major(t.to(dev), VF.DT_BF16 if dtype == "bf16" else VF.DT_F32, 64)
+    pm = VF.to_pixel_major(t.to(dev), VF.DT_BF16 if dtype == "bf16" else VF.DT_F32, t.shape[1])
     g = Guarded(pm.numel(), pm.dtype, dev, float("nan"))
     v = g.body.view(pm.shape)
     v.copy_(pm)
@@ -483,12 +494,12 @@ def pm_planes_input(t, dtype, dev):
 
 
 class PmOutput:
-    def __init__(self, n, h, w, dtype, dev, planes=1):
+    def __init__(self, n, h, w, dtype, dev, planes=1, c=64):
         tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
-        shape = (n, h, (w + 31) // 32, 8, 32, 8)
+        shape = (n, h, (w + 31) // 32, c // 8, 32, 8)
         numel = planes * int(np.prod(shape))
         self.g = Guarded(numel, tdt, dev, SENTINEL)
-        self.shape, self.planes, self.w = shape, planes, w
+        self.shape, self.planes, self.w, self.c = shape, planes, w, c
 
     def ptr(self):
         return self.g.body.data_ptr()
@@ -499,7 +510,7 @@ class PmOutput:
         outs = []
         for v in self.g.body.view(self.planes, *self.shape):
             v.pm_w = self.w
-            outs.append(VF.from_pixel_major(v, 64).cpu())
+            outs.append(VF.from_pixel_major(v, self.c).cpu())
         return outs[0] if self.planes == 1 else torch.stack(outs)
 
 

@@ -208,27 +208,31 @@ def _exported_vsr_symbols(path):
 
 def test_the_hooks_are_additions_to_an_unchanged_abi():
     """The library's exported `vsr_` symbols, enumerated from its dynamic symbol table: before the hooks it exported 74 -- the 67 of
-    include/vsrlab_hip.h (= EXPORTS) and 7 vsr_debug_* entries (OTHER_DEBUG_EXPORTS) -- and now exactly those plus the 7 new hooks:
-    nothing else, nothing missing.  The ABI number stays."""
+    include/vsrlab_hip.h (= EXPORTS) and 7 vsr_debug_* entries (OTHER_DEBUG_EXPORTS) -- and now exactly those plus the 7
+    reconstruction-tail hooks (81) and the 7 propagation-trunk hooks (88), by name: nothing else, nothing missing.  The ABI number stays."""
     L, lib = _lib()
     import os
     import re
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vsrlab_hip.h")).read()
     declared = set(re.findall(r"\b(vsr_[a-z0-9_]+)\s*\(", header))
     assert declared == set(L.EXPORTS) and len(L.EXPORTS) == 67 and lib.vsr_abi_version() == 4
-    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and len(L.DEBUG_SIGNATURES) == 7
+    tail = {"vsr_debug_tail_" + k for k in ("last2_fwd", "last2_dgrad", "planar_c64", "last2_wgrad", "conv_unshuffle", "ps_dgrad", "ps_wgrads")}
+    trunk = {"vsr_debug_trunk_" + k for k in ("conv", "stem", "stem_dgrad", "point", "wgrad_cc", "stem_wgrads", "chain")}
+    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk and len(tail | trunk) == 14
     assert not set(L.DEBUG_SIGNATURES) & declared and not set(L.DEBUG_SIGNATURES) & set(L.OTHER_DEBUG_EXPORTS)
     got = _exported_vsr_symbols(L.LIB_PATH)
     before = set(L.EXPORTS) | set(L.OTHER_DEBUG_EXPORTS)
     assert got - set(L.DEBUG_SIGNATURES) == before, (sorted(got - set(L.DEBUG_SIGNATURES) - before), sorted(before - got))
-    assert got - before == set(L.DEBUG_SIGNATURES)
+    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7
     for name in L.DEBUG_SIGNATURES:
         assert getattr(lib, name).argtypes == L.DEBUG_SIGNATURES[name][1]
 
 
 def test_hostcheck_program_passes_without_sanitizers(tmp_path):
-    """tools/hr_tail_hooks_hostcheck.hip (the hooks against stubbed launches; `make hooks_hostcheck` runs it under ASan / UBSan) built
-    plain and run: every refusal before any pack or launch, every accepted call's ConvArgs as given, and -- the one check of it that
+    """tools/hr_tail_hooks_hostcheck.hip and tools/trunk_hooks_hostcheck.hip (the hooks against stubbed launches; `make hooks_hostcheck`
+    runs both under ASan / UBSan) built plain and run.  The trunk program: every refusal before any pack or launch, and what the accepted
+    calls hand to vsr_launch_conv, vsr_launch_wgrad, vsr_launch_wgrad_reduce and vsr_launch_conv3x3_chain (segment counts, strides, i_off,
+    accumulate, layer offsets).  The tail program: every refusal before any pack or launch, every accepted call's ConvArgs as given, and -- the one check of it that
     no GPU test can make -- wgrad_launch() passes a 1- or 2-plane cotangent's plane count on to vsr_launch_last2_wgrad (it used to
     pass none, and the kernel read three planes: the surplus never reaches gw, so the values cannot show it)."""
     import os
@@ -238,7 +242,7 @@ def test_hostcheck_program_passes_without_sanitizers(tmp_path):
     env.setdefault("HIPCC", "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
     r = subprocess.run(["make", "-C", os.path.join(root, "vsrlab_amd", "csrc"), "hooks_hostcheck", "HOSTCHECK_SAN=",
                         f"HOSTCHECK_OUT={tmp_path}/hostcheck"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "hostcheck OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "\nhostcheck OK" in "\n" + r.stdout and "trunk hostcheck OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
 
 def test_hooks_refuse_null_pointers_and_bad_sizes_before_any_launch():

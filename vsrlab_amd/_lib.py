@@ -128,9 +128,10 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-# Test hooks of csrc/hr_tail_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in EXPORTS, like the other
-# vsr_debug_* entries, whose argument types the tests that call them set by hand).  These seven have long mixed int / long long /
-# float / pointer lists and three callers (both hr_tail tests, the driver), so their types are stated once, here; load() applies them.
+# Test hooks of csrc/hr_tail_hooks.hip and csrc/trunk_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in
+# EXPORTS, like the other vsr_debug_* entries, whose argument types the tests that call them set by hand).  These fourteen have long
+# mixed int / long long / float / pointer lists and three callers each (a host test, a GPU test, the driver), so their types are stated
+# once, here; load() applies them.
 # OTHER_DEBUG_EXPORTS: the library's remaining vsr_debug_* symbols.  EXPORTS + OTHER_DEBUG_EXPORTS + DEBUG_SIGNATURES is every
 # `vsr_` symbol the product library exports (tests/test_hr_tail_host.py enumerates its dynamic symbol table against this).
 OTHER_DEBUG_EXPORTS = ("vsr_debug_chain_inject_error", "vsr_debug_chain_item", "vsr_debug_chain_timeouts", "vsr_debug_chain_timing_begin",
@@ -144,6 +145,15 @@ DEBUG_SIGNATURES = {
     "vsr_debug_tail_conv_unshuffle": (c_int, [c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
     "vsr_debug_tail_ps_dgrad": (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "vsr_debug_tail_ps_wgrads": (c_int, [c_int, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
+    # csrc/trunk_hooks.hip (dtype, C first; the weight-gradient and chain entries take HOST arrays of device pointers / layer words)
+    "vsr_debug_trunk_conv": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_int, c_int,
+                                     c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_stem": (c_int, [c_int, c_int, c_int, _P, _P, _LL, _P, _P, _P, _P, c_int, c_float, c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_stem_dgrad": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _LL, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_point": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_wgrad_cc": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_stem_wgrads": (c_int, [c_int, c_int, c_int, _P, _LL, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_trunk_chain": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
 }
 
 _lib = None

@@ -270,8 +270,13 @@ __global__ __launch_bounds__(PNT, 1) void conv3x3_c64_persist_kernel(const ConvA
                                 const unsigned mw[4] = {mq.x, mq.y, mq.z, mq.w};
 #pragma unroll
                                 for (int jj = 0; jj < 4; ++jj) {
-                                    v[2 * jj] *= (bf_lo(mw[jj]) > 0.f ? 1.f : neg);
-                                    v[2 * jj + 1] *= (bf_hi(mw[jj]) > 0.f ? 1.f : neg);
+                                    if (MASK == MASK_RELU) {    // +0 where masked, as the sign-bit arm stores (a product with 0 keeps v's sign: -0)
+                                        v[2 * jj] = bf_lo(mw[jj]) > 0.f ? v[2 * jj] : 0.f;
+                                        v[2 * jj + 1] = bf_hi(mw[jj]) > 0.f ? v[2 * jj + 1] : 0.f;
+                                    } else {
+                                        v[2 * jj] *= (bf_lo(mw[jj]) > 0.f ? 1.f : neg);
+                                        v[2 * jj + 1] *= (bf_hi(mw[jj]) > 0.f ? 1.f : neg);
+                                    }
                                 }
                             }
                             C64_ARM_PLAIN(ow, v)

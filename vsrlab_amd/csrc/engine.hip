@@ -256,10 +256,8 @@ int pack_all_collect(const Ctx& c, const Plan& p, const float* const* prm) {
             CK(c.pack_bias(prm[ix.blk_b(dir, k)], c.at(p.blk_b[dir][k]), C));
         }
     }
-    for (int s = 0; s < 2; ++s) {
-        CK(c.pack(prm[ix.point_w()], c.at(p.point_w + (size_t)s * CO * C * p.es), 1, CO, C, C, C, 2 * C, s * C, 1, 0, 0));
-        if (p.bwd) CK(c.pack(prm[ix.point_w()], c.at(p.point_wd + (size_t)s * CO * C * p.es), 1, CO, C, C, C, 2 * C, s * C, 1, 0, 1));
-    }
+    CK(c.pack_point(prm[ix.point_w()], c.at(p.point_w), 0));
+    if (p.bwd) CK(c.pack_point(prm[ix.point_w()], c.at(p.point_wd), 1));
     CK(c.pack_bias(prm[ix.point_b()], c.at(p.point_b), C));
     for (int k = 0; k < p.ups; ++k) {
         CK(c.pack_ps(prm[ix.up_w(k)], c.at(p.up_w[k]), 0));
@@ -368,13 +366,9 @@ int last0_forward(const Ctx& c, const Plan& p, int i, void* sign_out) {
 
 int recon_forward(const Ctx& c, const Plan& p, int i, const float* lrs, float* sr) {
     const int n = p.n, h = p.h, w = p.w;
-    {
-        ConvArgs a = conv_args(n, h, w, c.C);       // point_conv on cat([outputs[i], feat_prop]) (basicvsr.py:75-77)
-        a.src[0] = c.at(p.feat[0][i]); a.src[1] = c.at(p.feat[1][i]);
-        a.wpack = c.at(p.point_w); a.bias = c.fat(p.point_b); a.dst[0] = c.at(p.Pt[i]); a.act = ACT_LEAKY;
-        CK(vsr_launch_conv(c.dtype, 1, 2, p.C, p.C, 0, p.CO, EPI_NHWC, a, c.st));
-        if (p.sb) CK(vsr_launch_sign_bits_c64(c.at(p.Pt[i]), c.at(p.SBPt[i]), n, h, w, c.st));   // mask of upsample.0's data gradient
-    }
+    // point_conv on cat([outputs[i], feat_prop]) (basicvsr.py:75-77)
+    CK(c.point_conv(c.at(p.feat[0][i]), c.at(p.feat[1][i]), c.at(p.point_w), c.fat(p.point_b), c.at(p.Pt[i]), n, h, w));
+    if (p.sb) CK(vsr_launch_sign_bits_c64(c.at(p.Pt[i]), c.at(p.SBPt[i]), n, h, w, c.st));   // mask of upsample.0's data gradient
     const int S = p.scale;                     // upscale: S / 2 PixelShufflePacks (basicvsr.py:19); U1 = U0 for S = 2 (Plan::build)
     CK(c.conv_ps(c.at(p.Pt[i]), c.at(p.up_w[0]), c.fat(p.up_b[0]), c.at(p.U0[i]), n, h, w));
     if (p.ups == 2) CK(c.conv_ps(c.at(p.U0[i]), c.at(p.up_w[1]), c.fat(p.up_b[1]), c.at(p.U1[i]), n, 2 * h, 2 * w));
@@ -551,12 +545,8 @@ int recon_backward(const Ctx& c, const Plan& p, int i, const float* lrs, const f
     // upsample.0 (at h x w): its input is LeakyReLU(point_conv) => mask with P
     CK(c.conv_ps_dgrad(c.at(gu0), c.at(p.up_wd[0]), c.at(gp), c.at(p.Pt[i]), MASK_LEAKY, n, h, w, p.sb ? c.at(p.SBPt[i]) : nullptr, p.unsh, false));
     if (!p.hrdef) CK(recon_ps_wgrads(c, p, 0, i, i + 1, g));
-    {   // point_conv dgrad: two 64-channel outputs (d outputs[i], d feat_prop)
-        ConvArgs a = conv_args(n, h, w, c.C);
-        a.src[0] = c.at(gp); a.wpack = c.at(p.point_wd); a.w_zstride = p.CO * C; a.nz = 2;
-        a.dst[0] = c.at(p.dFeatB[i]); a.dst[1] = c.at(p.dFF[i]);
-        CK(vsr_launch_conv(c.dtype, 1, 1, C, C, 0, p.CO, EPI_NHWC, a, c.st));
-    }
+    // point_conv dgrad: two C-channel outputs (d outputs[i], d feat_prop)
+    CK(c.point_dgrad(c.at(gp), c.at(p.point_wd), c.at(p.dFeatB[i]), c.at(p.dFF[i]), n, h, w));
     if (!p.hrdef) CK(recon_point_wgrads(c, p, i, i + 1, g));
     return VSR_OK;
 }

@@ -155,6 +155,27 @@ struct Ctx {
         return VSR_OK;
     }
 
+    // ---- the 1x1 fusion conv on cat([outputs[i], feat_prop]) (basicvsr.py:18,75-77) ----
+    // two weight sets, one per C-channel half of its 2C inputs; mode 0 forward, 1 data gradient
+    int pack_point(const float* w, void* dst, int mode) const {
+        for (int s = 0; s < 2; ++s) CK(pack(w, (char*)dst + (size_t)s * CO * C * es, 1, CO, C, C, C, 2 * C, s * C, 1, 0, mode));
+        return VSR_OK;
+    }
+    // y = LeakyReLU(conv1x1(cat([xa, xb])) + bias)
+    int point_conv(const void* xa, const void* xb, const void* wpack, const float* bias, void* y, int N, int H, int W) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.src[0] = xa; a.src[1] = xb;
+        a.wpack = wpack; a.bias = bias; a.dst[0] = y; a.act = ACT_LEAKY;
+        return vsr_launch_conv(dtype, 1, 2, C, C, 0, CO, EPI_NHWC, a, st);
+    }
+    // its data gradient: two C-channel outputs (towards xa, towards xb) of one launch
+    int point_dgrad(const void* dy, const void* wpackd, void* da, void* db, int N, int H, int W) const {
+        ConvArgs a = conv_args(N, H, W, C);
+        a.src[0] = dy; a.wpack = wpackd; a.w_zstride = CO * C; a.nz = 2;
+        a.dst[0] = da; a.dst[1] = db;
+        return vsr_launch_conv(dtype, 1, 1, C, C, 0, CO, EPI_NHWC, a, st);
+    }
+
     // ---- SPyNet layer j (spynet.py:16-18) ----
     // mode 0: forward weights; mode 1: data-gradient weights, rows = the conv's input channels (template COUT of the dgrad launch), K = its outputs
     int pack_spy(int j, const float* w, void* dst, int mode) const {

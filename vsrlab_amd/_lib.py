@@ -54,6 +54,12 @@ class RaftCorrDesc(ctypes.Structure):
     _fields_ = [(k, c_int) for k in ("N", "D", "H", "W", "levels", "radius", "dtype")]
 
 
+class SpatialCorrDesc(ctypes.Structure):
+    """struct VsrSpatialCorrDesc (include/vsrlab_spatial_corr.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "C", "H", "W", "patch_h", "patch_w", "stride_h", "stride_w", "pad_h", "pad_w", "dil_h", "dil_w",
+                                     "dtype")] + [("scale", c_float)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -156,7 +162,35 @@ DEBUG_SIGNATURES = {
     "vsr_debug_trunk_chain": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
 }
 
+# libvsrlab_spatial_corr.so (include/vsrlab_spatial_corr.h): the local correlation, a library of its own -- the symbols that
+# libvsrlab_hip.so exports are pinned and stay as they are
+SPATIAL_CORR_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_spatial_corr.so")
+SPATIAL_CORR_SIGNATURES = {
+    "vsr_spatial_corr_workspace_bytes": (c_size_t, [ctypes.POINTER(SpatialCorrDesc)]),
+    "vsr_spatial_corr_fwd": (c_int, [ctypes.POINTER(SpatialCorrDesc), _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_spatial_corr_bwd": (c_int, [ctypes.POINTER(SpatialCorrDesc), _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+SPATIAL_CORR_EXPORTS = tuple(SPATIAL_CORR_SIGNATURES)
+
 _lib = None
+_spatial_corr_lib = None
+
+
+def load_spatial_corr():
+    """Load libvsrlab_spatial_corr.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
+    global _spatial_corr_lib
+    if _spatial_corr_lib is None:
+        if not os.path.exists(SPATIAL_CORR_LIB_PATH):
+            raise RuntimeError(
+                f"vsrlab_amd: HIP library not built ({SPATIAL_CORR_LIB_PATH} missing). Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
+        lib = ctypes.CDLL(SPATIAL_CORR_LIB_PATH)
+        for name, (res, args) in SPATIAL_CORR_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _spatial_corr_lib = lib
+    return _spatial_corr_lib
 
 
 def load():

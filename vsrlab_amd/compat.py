@@ -14,7 +14,7 @@ def install_as_vsrlab(force: bool = False) -> None:
     if "vsrlab" in sys.modules and sys.modules["vsrlab"] is not vsrlab_amd and not force:
         raise RuntimeError("a different `vsrlab` package is already imported; pass force=True to shadow it")
     sys.modules["vsrlab"] = vsrlab_amd
-    for sub in ("core", "core.modules", "core.modules.conv", "core.modules.upsampling", "core.losses", "vsr", "vsr.models",
+    for sub in ("core", "core.modules", "core.modules.conv", "core.modules.upsampling", "core.modules.correlation", "core.losses", "vsr", "vsr.models",
                 "vsr.models.RealBasicVSR", "vsr.models.RealBasicVSR.realbasicvsr", "vsr.models.RealBasicVSR.modules",
                 "vsr.models.RealBasicVSR.modules.basicvsr", "vsr.models.RealBasicVSR.modules.spynet",
                 "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.modules",
@@ -22,7 +22,7 @@ def install_as_vsrlab(force: bool = False) -> None:
                 "core.utils", "core.metrics", "train_gan", "optical_flow",
                 "optical_flow.models", "optical_flow.models.spynet", "optical_flow.models.raft", "optical_flow.models.raft.raft",
                 "optical_flow.models.raft.corr", "optical_flow.models.raft.extractor", "optical_flow.models.raft.update",
-                "optical_flow.models.raft.utils"):
+                "optical_flow.models.raft.utils", "optical_flow.models.irr", "optical_flow.models.irr.pwc_modules"):
         sys.modules["vsrlab." + sub] = importlib.import_module("vsrlab_amd." + sub)
 
 

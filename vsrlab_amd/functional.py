@@ -1597,3 +1597,93 @@ def raft_correlation(coords: torch.Tensor, fmap1: torch.Tensor, fmap2: torch.Ten
                      compute_dtype: Optional[str] = None) -> torch.Tensor:
     """The reference's ``correlation(coords, fmap1, fmap2, num_levels, radius)`` in one call: pyramid + one lookup."""
     return raft_corr_lookup(raft_corr_pyramid(fmap1, fmap2, num_levels, compute_dtype, radius=radius), coords)
+
+
+# --------------------------------------------------------------------------------------------- #
+# Local correlation: SpatialCorrelationSampler and PWC's cost volume in one launch
+# (reference: core/modules/correlation.py, optical_flow/models/irr/pwc_modules.py:39-59; csrc/spatial_corr.hip,
+# built into libvsrlab_spatial_corr.so)
+# --------------------------------------------------------------------------------------------- #
+_SPATIAL_CORR_UNSUPPORTED = ("vsrlab_amd: spatial_correlation: unsupported shape (patch odd and <= 9, stride 1 or 2, dilation_patch 1 or 2, "
+                             "0 <= padding <= dilation_patch * (patch - 1) / 2, each per axis): inputs {shape}, patch_size {patch}, "
+                             "stride {stride}, padding {padding}, dilation_patch {dil}")
+
+
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def _spatial_corr_desc(shape, patch, stride, padding, dil, dtype, scale):
+    n, c, h, w = (int(v) for v in shape)
+    return _lib.SpatialCorrDesc(n, c, h, w, *patch, *stride, *padding, *dil, int(dtype), float(scale))
+
+
+def spatial_corr_workspace_bytes(shape, patch_size=1, stride=1, padding=0, dilation_patch=1, dtype: int = DT_F32) -> int:
+    """Bytes of the workspace of one ``spatial_correlation`` call on inputs of ``shape`` (N, C, H, W); 0: unsupported.  Host
+    arithmetic only."""
+    desc = _spatial_corr_desc(shape, _pair(patch_size), _pair(stride), _pair(padding), _pair(dilation_patch), dtype, 1.0)
+    return int(_lib.load_spatial_corr().vsr_spatial_corr_workspace_bytes(ctypes.byref(desc)))
+
+
+class _SpatialCorrFn(torch.autograd.Function):
+    """Both gradients are gathers with one owner per element: bit-identical across runs."""
+
+    @staticmethod
+    def forward(ctx, input1, input2, cfg):
+        desc, nbytes, out_shape, need_bwd = cfg
+        lib = _lib.load_spatial_corr()
+        a, b = _f32c(input1), _f32c(input2)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        out = torch.empty(out_shape, dtype=torch.float32, device=a.device)
+        _lib.check(lib.vsr_spatial_corr_fwd(ctypes.byref(desc), _ptr(a), _ptr(b), _ptr(out), _ptr(ws), nbytes, _stream()), "spatial_corr_fwd")
+        del ws
+        ctx.desc, ctx.nbytes = desc, nbytes
+        ctx.saved = (a, b) if need_bwd else None
+        ctx.backward_done = False
+        ctx.dtypes = (input1.dtype, input2.dtype)
+        return out.to(input1.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        if torch.is_grad_enabled():
+            raise RuntimeError("vsrlab_amd: spatial_correlation has no double backward (create_graph=True is not supported)")
+        if ctx.backward_done:
+            raise RuntimeError("vsrlab_amd: trying to backward through spatial_correlation a second time")
+        if ctx.saved is None:
+            raise RuntimeError("vsrlab_amd: backward through a spatial_correlation that ran without a gradient")
+        (a, b), ctx.saved, ctx.backward_done = ctx.saved, None, True
+        gout = _f32c(gout)
+        need = ctx.needs_input_grad
+        d1 = torch.empty_like(a) if need[0] else None
+        d2 = torch.empty_like(b) if need[1] else None
+        ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=a.device)
+        _lib.check(_lib.load_spatial_corr().vsr_spatial_corr_bwd(ctypes.byref(ctx.desc), _ptr(a), _ptr(b), _ptr(gout), _ptr(d1), _ptr(d2), _ptr(ws),
+                                                    ctx.nbytes, _stream()), "spatial_corr_bwd")
+        del ws
+        return (None if d1 is None else d1.to(ctx.dtypes[0]), None if d2 is None else d2.to(ctx.dtypes[1]), None)
+
+
+def spatial_correlation(input1: torch.Tensor, input2: torch.Tensor, patch_size=1, stride=1, padding=0, dilation_patch=1,
+                        scale: float = 1.0, compute_dtype: Optional[str] = None) -> torch.Tensor:
+    """(N, P_h, P_w, ceil(H' / s_h), ceil(W' / s_w)) in the dtype of ``input1``:
+    ``out[n, i, j, y, x] = scale * sum_c in1[n, c, y s_h, x s_w] * in2[n, c, y s_h + i d_h - m_h, x s_w + j d_w - m_w]`` in the
+    frame zero-padded by ``padding`` (H' x W'), ``in2`` zero outside it, ``m = dilation_patch * (patch_size - 1) // 2``.  Every
+    int-or-pair argument is (vertical, horizontal); ``i`` (slow) is the vertical displacement index.  One kernel launch reads
+    each map once; storage is fp32, or bf16 under ``compute_dtype='bf16'`` (fp32 accumulation either way).  Differentiable in
+    both inputs.  There is no CPU fallback."""
+    if input1.dim() != 4 or input1.shape != input2.shape:
+        raise ValueError(f"spatial_correlation: input1 and input2 must have one shape (N, C, H, W); got {tuple(input1.shape)} and {tuple(input2.shape)}")
+    patch, strd, pad, dil = _pair(patch_size), _pair(stride), _pair(padding), _pair(dilation_patch)
+    if min(patch) < 1 or min(strd) < 1 or min(pad) < 0 or min(dil) < 1 or input1.numel() == 0:
+        raise ValueError(f"spatial_correlation: patch_size, stride and dilation_patch must be positive, padding non-negative and the inputs "
+                         f"non-empty; got {patch}, {strd}, {dil}, {pad}, {tuple(input1.shape)}")
+    dtype = resolve_dtype(compute_dtype)
+    desc = _spatial_corr_desc(input1.shape, patch, strd, pad, dil, dtype, scale)
+    nbytes = int(_lib.load_spatial_corr().vsr_spatial_corr_workspace_bytes(ctypes.byref(desc)))
+    if nbytes == 0:
+        raise RuntimeError(_SPATIAL_CORR_UNSUPPORTED.format(shape=tuple(input1.shape), patch=patch, stride=strd, padding=pad, dil=dil))
+    _require_gpu(input1, input2)
+    n, _, h, w = (int(v) for v in input1.shape)
+    out_shape = (n, patch[0], patch[1], -(-(h + 2 * pad[0]) // strd[0]), -(-(w + 2 * pad[1]) // strd[1]))
+    need_bwd = torch.is_grad_enabled() and (input1.requires_grad or input2.requires_grad)
+    return _SpatialCorrFn.apply(input1, input2, (desc, nbytes, out_shape, need_bwd))

@@ -13,8 +13,7 @@ import zlib
 import torch
 import torch.nn.functional as F
 
-from deform_common import BIG, bf16_store, grad_stats, sub_stride  # noqa: F401  (shared fixture helpers)
-from raft_common import _st
+from helpers import BIG, _st, bf16_store, grad_stats, sub_stride  # noqa: F401  (the host tests read them here)
 
 # name: (N, C, H, W), patch, stride, padding, dilation_patch -- the cases of the golden and of the GPU tests
 CASES = {

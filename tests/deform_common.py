@@ -7,9 +7,7 @@ torchvision is not installed anywhere this project is built or tested; this rest
 backward products -- the restatement rounds too (``bf16_store``); None = exact."""
 import torch
 
-
-def bf16_store(t):
-    return t.to(torch.bfloat16).to(t.dtype)
+from helpers import BIG, bf16_store, grad_stats, sub_stride  # noqa: F401  (the host tests read them here)
 
 
 class _RoundGrad(torch.autograd.Function):
@@ -133,17 +131,3 @@ def block_state_dict(module_sd, dtype=torch.float64):
         s = 1.0 if k.endswith("bias") else (c["oscale"] if "conv_offset" in k else c["wscale"])
         out[k] = keyed("dblock." + k, v.shape, s, dtype)
     return out
-
-
-BIG = 8192       # tensors above this many elements are pinned by (sum, norm, <g, proj_vector>) and every stride-th element
-SUB = 2048
-
-
-def sub_stride(numel):
-    return -(-numel // SUB)
-
-
-def grad_stats(key, g):
-    from helpers import proj_vector
-    g = g.detach().double().cpu()
-    return torch.stack([g.sum(), g.norm(), (g * proj_vector(key, tuple(g.shape))).sum()])

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 
 import correlation_common as CC  # noqa: E402
+from helpers import BIG, grad_stats, sub_stride  # noqa: E402
 
 
 def load_by_path(name, path):
@@ -33,11 +34,11 @@ def load_by_path(name, path):
 
 def put(store, tag, key, g):
     g = g.detach()
-    if g.numel() <= CC.BIG:
+    if g.numel() <= BIG:
         store[f"{tag}__{key}"] = g.numpy().astype(np.float64)
     else:
-        store[f"{tag}__sub__{key}"] = g.flatten()[::CC.sub_stride(g.numel())].numpy().astype(np.float64)
-    store[f"{tag}__stats__{key}"] = CC.grad_stats(f"correlation.{tag}.{key}", g).numpy()
+        store[f"{tag}__sub__{key}"] = g.flatten()[::sub_stride(g.numel())].numpy().astype(np.float64)
+    store[f"{tag}__stats__{key}"] = grad_stats(f"correlation.{tag}.{key}", g).numpy()
 
 
 def main(ref_src):

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import deform_common as DC  # noqa: E402
+from helpers import BIG, grad_stats, sub_stride  # noqa: E402
 from make_golden import import_reference  # noqa: E402
 
 
@@ -36,11 +37,11 @@ def check_exercised(offset, mask, tanh_in, H, W, tag):
 
 
 def put(store, tag, key, g):
-    if g.numel() <= DC.BIG:
+    if g.numel() <= BIG:
         store[f"{tag}__{key}"] = g.detach().numpy().astype(np.float64)
     else:                                    # every stride-th element in full precision, the whole through its statistics
-        store[f"{tag}__sub__{key}"] = g.detach().flatten()[::DC.sub_stride(g.numel())].numpy().astype(np.float64)
-    store[f"{tag}__stats__{key}"] = DC.grad_stats(f"{tag}.{key}", g).numpy()
+        store[f"{tag}__sub__{key}"] = g.detach().flatten()[::sub_stride(g.numel())].numpy().astype(np.float64)
+    store[f"{tag}__stats__{key}"] = grad_stats(f"{tag}.{key}", g).numpy()
 
 
 def main():

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 
 import raft_common as RC  # noqa: E402
+from helpers import BIG, grad_stats, sub_stride  # noqa: E402
 
 
 def import_reference(ref_src):
@@ -56,11 +57,11 @@ def import_reference(ref_src):
 
 def put(store, tag, key, g):
     g = g.detach()
-    if g.numel() <= RC.BIG:
+    if g.numel() <= BIG:
         store[f"{tag}__{key}"] = g.numpy().astype(np.float64)
     else:
-        store[f"{tag}__sub__{key}"] = g.flatten()[::RC.sub_stride(g.numel())].numpy().astype(np.float64)
-    store[f"{tag}__stats__{key}"] = RC.grad_stats(f"raft.{tag}.{key}", g).numpy()
+        store[f"{tag}__sub__{key}"] = g.flatten()[::sub_stride(g.numel())].numpy().astype(np.float64)
+    store[f"{tag}__stats__{key}"] = grad_stats(f"raft.{tag}.{key}", g).numpy()
 
 
 def main(ref_src):

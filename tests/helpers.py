@@ -53,3 +53,35 @@ def realbasicvsr_oracle_grads(sd64, lr, cot_sr, cot_lq):
     sr, lq = O.realbasicvsr_forward(leaves, lr)
     (torch.mean(sr * cot_sr) + torch.mean(lq * cot_lq)).backward()
     return sr.detach(), lq.detach(), {k: v.grad for k, v in leaves.items() if v.grad is not None}
+
+
+# ---- fixture helpers of the gather-op families (deform_common.py, raft_common.py, correlation_common.py and their goldens) ----
+def bf16_store(t):
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class _StoreST(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, store):
+        return store(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def _st(x, store):
+    return x if store is None else _StoreST.apply(x, store)
+
+
+BIG = 8192       # tensors above this many elements are pinned by (sum, norm, <g, proj_vector>) and every stride-th element
+SUB = 2048
+
+
+def sub_stride(numel):
+    return -(-numel // SUB)
+
+
+def grad_stats(key, g):
+    g = g.detach().double().cpu()
+    return torch.stack([g.sum(), g.norm(), (g * proj_vector(key, tuple(g.shape))).sum()])

@@ -14,24 +14,10 @@ import math
 import torch
 import torch.nn.functional as F
 
-from deform_common import BIG, bf16_store, grad_stats, sub_stride  # noqa: F401  (shared fixture helpers)
+from helpers import BIG, _st, bf16_store, grad_stats, sub_stride  # noqa: F401  (the host tests read them here)
 
 RADIUS = 3
 TAPS = (2 * RADIUS + 1) ** 2
-
-
-class _StoreST(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, store):
-        return store(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-def _st(x, store):
-    return x if store is None else _StoreST.apply(x, store)
 
 
 def level_sizes(H, W, num_levels):

@@ -9,7 +9,7 @@ import torch
 
 import correlation_common as CC
 from attention_common import GUARD, SENTINEL, _guarded
-from helpers import rel_err, rel_l2
+from helpers import bf16_store, rel_err, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +21,7 @@ def _dev():
 @pytest.fixture(scope="module")
 def oracle():
     """per case: the fp64 restatement and its bf16-storage twin (out, d input1, d input2), computed once"""
-    return {case: (CC.restate(case), CC.restate(case, store=CC.bf16_store)) for case in CC.CASES}
+    return {case: (CC.restate(case), CC.restate(case, store=bf16_store)) for case in CC.CASES}
 
 
 def _hip(case, compute_dtype, grad=(True, True), via=None):
@@ -145,7 +145,7 @@ def test_cost_volume(dt, oracle):
     if dt == "fp32":
         assert max(e) < 1e-3, e
     else:
-        floor = _errors(CC.restate_cost_volume(store=CC.bf16_store), exact)
+        floor = _errors(CC.restate_cost_volume(store=bf16_store), exact)
         for g, fl in zip(e, floor):
             assert g <= 1.5 * max(fl, 1e-3), (e, floor)
 

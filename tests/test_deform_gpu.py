@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import deform_common as DC
-from helpers import GOLDEN, proj_vector, rel_err, rel_l2
+from helpers import GOLDEN, bf16_store, proj_vector, rel_err, rel_l2, sub_stride
 
 pytestmark = pytest.mark.gpu
 TOL32 = 1e-3
@@ -98,13 +98,14 @@ def _errors(y, g, y_o, g_o, d, mode, H, W):
 
 
 SHAPES = [dict(N=2, C=32, Cout=32, H=13, W=37, dg=4), dict(N=1, C=120, Cout=120, H=11, W=21, dg=12),
-          dict(N=1, C=64, Cout=64, H=9, W=19, dg=1)]
+          dict(N=1, C=64, Cout=64, H=9, W=19, dg=1), dict(N=2, C=9, Cout=8, H=13, W=37, dg=3)]
 
 
 @pytest.mark.parametrize("mode", ["plain", "mask", "flow"])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"C{s['C']}dg{s['dg']}")
 def test_fp32_matches_the_fp64_restatement(mode, shape):
-    """odd shapes: W not a multiple of 32, H*W not a multiple of the 32- and 64-pixel tiles; cpg 8, 10 (padded to 16) and 64"""
+    """odd shapes: W not a multiple of 32, H*W not a multiple of the 32- and 64-pixel tiles; cpg 8, 10 (padded to 16) and 64;
+    C9dg3: groups of 3 in slots of 8, 24 packed channels in a staged row of 32, 8 outputs in an accumulator block of 32"""
     dev = _gpu()
     d = _inputs(7, mode=mode, **shape)
     y, g = _hip(d, mode, dev, "fp32")
@@ -123,7 +124,7 @@ def test_bf16_within_the_noise_floor(mode):
     d = _inputs(9, mode=mode, **shape)
     y, g = _hip(d, mode, dev, "bf16")
     y_o, g_o = _oracle(d, mode)
-    y_e, g_e = _oracle(d, mode, store=DC.bf16_store)
+    y_e, g_e = _oracle(d, mode, store=bf16_store)
     e = _errors(y, g, y_o, g_o, d, mode, shape["H"], shape["W"])
     e_emu = _errors(y_e, g_e, y_o, g_o, d, mode, shape["H"], shape["W"])
     print("bf16", mode, "hip", e, "restatement", e_emu)
@@ -200,8 +201,8 @@ def _check_golden(z, tag, key, val, tol):
     if f"{tag}__{key}" in z.files:
         e = rel_l2(val, torch.from_numpy(z[f"{tag}__{key}"]))
     else:
-        e = float((val.flatten()[::DC.sub_stride(val.numel())] - torch.from_numpy(z[f"{tag}__sub__{key}"])).norm() / stats[1] *
-                  DC.sub_stride(val.numel()) ** 0.5)
+        e = float((val.flatten()[::sub_stride(val.numel())] - torch.from_numpy(z[f"{tag}__sub__{key}"])).norm() / stats[1] *
+                  sub_stride(val.numel()) ** 0.5)
     e_norm = abs(float(val.norm() / stats[1]) - 1)
     e_proj = abs(float((val * proj_vector(f"{tag}.{key}", tuple(val.shape))).sum() - stats[2])) / float(stats[1])
     print(tag, key, f"rel-L2 {e:.2e} norm {e_norm:.2e} proj {e_proj:.2e}")
@@ -311,7 +312,7 @@ def test_full_size_bf16():
     for n in range(0, N, 5):                           # the restatement, one image at a time (3.8 GB of columns per 15)
         sl = slice(n, n + 1)
         y32 = DC.flow_guided_deform_conv_ref(x[sl], raw[sl], flow[sl], w, b, 10.0)
-        y16 = DC.flow_guided_deform_conv_ref(x[sl], raw[sl], flow[sl], w, b, 10.0, store=DC.bf16_store)
+        y16 = DC.flow_guided_deform_conv_ref(x[sl], raw[sl], flow[sl], w, b, 10.0, store=bf16_store)
         e_hip, e_emu = max(e_hip, rel_err(y[sl], y32)), max(e_emu, rel_err(y16, y32))
     print(f"full size bf16: y max-rel {e_hip:.3e}, bf16-storage restatement {e_emu:.3e}")
     assert e_hip <= 1.5 * max(e_emu, FLOOR16)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import raft_common as RC
-from helpers import GOLDEN, rel_err, rel_l2
+from helpers import GOLDEN, bf16_store, rel_err, rel_l2, sub_stride
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ def _restate(case, store=None, dtype=torch.float64):
 @pytest.fixture(scope="module")
 def oracle():
     """per case: the fp64 restatement and its bf16-storage twin (out, d fmap1, d fmap2), computed once"""
-    return {case: (_restate(case), _restate(case, store=RC.bf16_store)) for case in CASES}
+    return {case: (_restate(case), _restate(case, store=bf16_store)) for case in CASES}
 
 
 def _hip(case, compute_dtype, one_shot=False, grad=True):
@@ -150,7 +150,7 @@ def test_peak_memory_has_no_room_for_a_volume():
 # ---- RAFT-small and the loss ---------------------------------------------------------------------------------------------------
 def _golden_sub(z, tag, key, value):
     v = value.detach().double().cpu()
-    return rel_err(v.flatten()[::RC.sub_stride(v.numel())], torch.from_numpy(z[f"{tag}__sub__{key}"]))
+    return rel_err(v.flatten()[::sub_stride(v.numel())], torch.from_numpy(z[f"{tag}__sub__{key}"]))
 
 
 @pytest.fixture(scope="module")
@@ -178,8 +178,8 @@ def raft_oracle():
     b64, c64 = model(torch.float64, None), loss(torch.float64, None)
     assert _golden_sub(z, "b", "flow_up", b64[0]) < 1e-6 and _golden_sub(z, "b", "dref", b64[1]) < 1e-6
     assert abs(float(c64[0]) / float(z["c__loss"]) - 1) < 1e-6 and _golden_sub(z, "c", "dsr", c64[1]) < 1e-6
-    return {"b": {None: b64, "fp32": model(torch.float32, None), "bf16": model(torch.float32, RC.bf16_store)},
-            "c": {None: c64, "fp32": loss(torch.float32, None), "bf16": loss(torch.float32, RC.bf16_store)}}
+    return {"b": {None: b64, "fp32": model(torch.float32, None), "bf16": model(torch.float32, bf16_store)},
+            "c": {None: c64, "fp32": loss(torch.float32, None), "bf16": loss(torch.float32, bf16_store)}}
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])

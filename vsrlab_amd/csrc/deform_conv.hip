@@ -2,9 +2,9 @@
 // flow-guided alignment (vsr/models/VRT/modules/deform_conv.py:133-145) fused into it, forward and backward.  DESIGN section 11c.
 //
 // Layout.  x is staged once per call from planar fp32 into channels-last [N][H*W][XC] of T (bf16 or fp32): a gather wants one
-// pixel's channels contiguous.  Every deformable group is padded to cpgp = 8 (cpg <= 8) or a multiple of 16 channels and XC is a
-// multiple of 32, so a 8-channel piece never straddles two groups and one bilinear set-up serves a whole piece.  Padding channels
-// are zero in x and in the packed weights.
+// pixel's channels contiguous (cl_stage.h, one tile of width XC with the group map; d x comes back the same way).  Every deformable
+// group is padded to cpgp = 8 (cpg <= 8) or a multiple of 16 channels and XC is a multiple of 32, so a 8-channel piece never
+// straddles two groups and one bilinear set-up serves a whole piece.  Padding channels are zero in x and in the packed weights.
 //
 // Forward / data backward: one wave owns 32 consecutive pixels of one image; the pixel is the MFMA column (lane & 31), so each
 // lane gathers its own pixel's operand fragment straight from HBM/L2 and no column tile ever exists in memory.
@@ -16,11 +16,12 @@
 // the K index of this product) and keeps all Cout x Cin accumulator blocks of its tap in registers; partial slabs + a reduction
 // launch in a fixed order (bit-identical across runs), as wgrad_mfma.hip does.
 #include "elt.h"
+#include "cl_stage.h"
 #include "host.h"
 
 namespace {
 
-constexpr int DC_MAXC = 192;            // Cin, Cout and the padded channel count XC
+constexpr int DC_MAXC = CL_MAXW;        // Cin, Cout and the padded channel count XC, which is one cl_stage.h tile: 192
 constexpr int DC_MAXOB = DC_MAXC / 32;  // 32-row accumulator blocks
 constexpr int DC_MAXOC = DC_MAXC / 16;  // 16-deep K steps over Cout
 constexpr int DC_WPIX = 64;             // pixels per weight-gradient tile
@@ -370,37 +371,7 @@ __global__ __launch_bounds__(256) void deform_bgrad_kernel(const float* dy, floa
     if (t == 0) gb[o] = red[0];
 }
 
-// ---- staging ----------------------------------------------------------------------------------------------------------
-// planar fp32 (N, Cin, H, W) -> channels-last [N][HW][XC] of T with the groups padded; 32 pixels per workgroup
-template <typename T>
-__global__ __launch_bounds__(256) void deform_stage_kernel(const float* x, T* xs, int Cin, int HW, int cpg, int cpgp, int XC) {
-    __shared__ float tile[32 * (DC_MAXC + 1)];
-    const int n = blockIdx.y, p0 = blockIdx.x * 32, t = threadIdx.x, ld = XC + 1;
-    for (int i = t; i < 32 * ld; i += 256) tile[i] = 0.f;
-    __syncthreads();
-    const int px = t & 31;
-    if (p0 + px < HW)
-        for (int c = t >> 5; c < Cin; c += 8) tile[px * ld + (c / cpg) * cpgp + c % cpg] = x[((long long)n * Cin + c) * HW + p0 + px];
-    __syncthreads();
-    for (int i = t; i < 32 * XC; i += 256) {
-        const int q = i / XC, c = i % XC;
-        if (p0 + q < HW) xs[((long long)n * HW + p0 + q) * XC + c] = (T)tile[q * ld + c];
-    }
-}
-// its adjoint for the fp32 d x accumulator
-__global__ __launch_bounds__(256) void deform_unstage_kernel(const float* acc, float* dx, int Cin, int HW, int cpg, int cpgp, int XC) {
-    __shared__ float tile[32 * (DC_MAXC + 1)];
-    const int n = blockIdx.y, p0 = blockIdx.x * 32, t = threadIdx.x, ld = XC + 1;
-    for (int i = t; i < 32 * XC; i += 256) {
-        const int q = i / XC, c = i % XC;
-        tile[q * ld + c] = p0 + q < HW ? acc[((long long)n * HW + p0 + q) * XC + c] : 0.f;
-    }
-    __syncthreads();
-    const int px = t & 31;
-    if (p0 + px < HW)
-        for (int c = t >> 5; c < Cin; c += 8) dx[((long long)n * Cin + c) * HW + p0 + px] = tile[px * ld + (c / cpg) * cpgp + c % cpg];
-}
-
+// ---- packing ----------------------------------------------------------------------------------------------------------
 // weights (Cout, Cin, 3, 3) fp32 -> MFMA A fragments, 512 elements (64 lanes x 8) per (tap, K step, row block):
 //   mode 0 (forward):  [tap][XC/16][CoutP/32]: lane (i, h), e -> W[cout 32 ob + i][channel 16 kc + 8 h + e]
 //   mode 1 (backward): [tap][XC/32][CoutP/16]: lane (i, h), e -> W[cout 16 oc + 8 h + e][channel 32 cb + i]
@@ -470,9 +441,7 @@ int deform_plan(const VsrDeformDesc* d, int backward, DeformPlan& pl) {
 
 template <typename T>
 int deform_prepare(const VsrDeformDesc* d, const DeformPlan& pl, const float* x, const float* weight, int mode, char* ws, hipStream_t st) {
-    const int HW = d->H * d->W;
-    hipLaunchKernelGGL(deform_stage_kernel<T>, dim3(cdiv(HW, 32), d->N), dim3(256), 0, st, x, reinterpret_cast<T*>(ws + pl.xs), d->Cin, HW,
-                       pl.cpg, pl.cpgp, pl.XC);
+    cl_pack<0>(st, d->N, d->Cin, d->H * d->W, pl.XC, ClGroups{pl.cpg, pl.cpgp}, x, reinterpret_cast<T*>(ws + pl.xs));
     hipLaunchKernelGGL(deform_pack_kernel<T>, dim3(cdiv(9 * pl.XC * pl.CoutP, 256)), dim3(256), 0, st, weight, reinterpret_cast<T*>(ws + pl.wpack),
                        mode, d->Cout, d->Cin, pl.cpg, pl.cpgp, d->deform_groups, pl.XC, pl.CoutP);
     HIP_CHECK_RET(hipGetLastError());
@@ -552,7 +521,7 @@ int vsr_deform_conv_bwd(const VsrDeformDesc* d, const float* x, const float* off
         if (bf) hipLaunchKernelGGL(deform_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(deform_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, a);
         HIP_CHECK_RET(hipGetLastError());
-        if (dx) hipLaunchKernelGGL(deform_unstage_kernel, dim3(cdiv(HW, 32), d->N), dim3(256), 0, st, a.dxacc, dx, d->Cin, HW, pl.cpg, pl.cpgp, pl.XC);
+        if (dx) cl_unpack<0>(st, d->N, d->Cin, HW, pl.XC, ClGroups{pl.cpg, pl.cpgp}, a.dxacc, dx);
     }
     if (dweight) {
         a.slab = reinterpret_cast<float*>(ws + pl.slab);

@@ -23,6 +23,7 @@
 // Coordinates are clamped in float to [-8, size + 7] before floor(): a window that far out has no tap inside either way, and
 // no huge or non-finite coordinate reaches an integer conversion or an address.
 #include "elt.h"
+#include "cl_stage.h"
 #include "host.h"
 
 namespace {
@@ -32,7 +33,6 @@ constexpr int RC_R = 3;                 // window radius
 constexpr int RC_TAPS = 49;
 constexpr int RC_MAXL = 4;
 constexpr int RC_QT = 32;               // queries per workgroup
-constexpr int RC_PT = 32;               // pixels per pack / unpack tile
 
 struct RaftArgs {
     const void* f1;                     // packed fmap1
@@ -208,32 +208,7 @@ __global__ __launch_bounds__(256) void raft_lookup_bwd_kernel(RaftArgs a) {
     }
 }
 
-// ---- pack, pool and their adjoints --------------------------------------------------------------------------------------
-// planar fp32 (N, D, HW) -> pixel-major [N][HW][D] of T
-template <typename T>
-__global__ __launch_bounds__(256) void raft_pack_kernel(const float* x, T* dst, int HW) {
-    __shared__ float tile[RC_PT][RC_D + 1];
-    const int n = blockIdx.y, p0 = blockIdx.x * RC_PT, t = threadIdx.x, px = t & 31;
-    if (p0 + px < HW)
-        for (int c = t >> 5; c < RC_D; c += 8) tile[px][c] = x[((long long)n * RC_D + c) * HW + p0 + px];
-    __syncthreads();
-    for (int i = t; i < RC_PT * RC_D; i += 256) {
-        const int q = i / RC_D, c = i % RC_D;
-        if (p0 + q < HW) dst[((long long)n * HW + p0 + q) * RC_D + c] = (T)tile[q][c];
-    }
-}
-// pixel-major fp32 -> planar fp32
-__global__ __launch_bounds__(256) void raft_unpack_kernel(const float* src, float* x, int HW) {
-    __shared__ float tile[RC_PT][RC_D + 1];
-    const int n = blockIdx.y, p0 = blockIdx.x * RC_PT, t = threadIdx.x, px = t & 31;
-    for (int i = t; i < RC_PT * RC_D; i += 256) {
-        const int q = i / RC_D, c = i % RC_D;
-        tile[q][c] = p0 + q < HW ? src[((long long)n * HW + p0 + q) * RC_D + c] : 0.f;
-    }
-    __syncthreads();
-    if (p0 + px < HW)
-        for (int c = t >> 5; c < RC_D; c += 8) x[((long long)n * RC_D + c) * HW + p0 + px] = tile[px][c];
-}
+// ---- pool and its adjoint (pack and unpack: cl_stage.h in full RC_D-channel rows) ------------------------------------
 // level (N, Hf, Wf) -> its 2 x 2 mean (N, Hc, Wc), Hc = Hf / 2, Wc = Wf / 2: one thread per pixel and 8-channel chunk
 template <typename T>
 __global__ __launch_bounds__(256) void raft_pool_kernel(const T* fine, T* coarse, int Hf, int Wf, int Hc, int Wc, long long chunks) {
@@ -302,10 +277,8 @@ RaftArgs raft_args(const VsrRaftCorrDesc* d, const RaftPlan& pk, const void* pac
 
 template <typename T>
 void raft_build(const VsrRaftCorrDesc* d, const RaftPlan& pl, const float* fmap1, const float* fmap2, char* pk, hipStream_t st) {
-    const int HW = d->H * d->W;
-    const dim3 grid(cdiv(HW, RC_PT), d->N);
-    hipLaunchKernelGGL(raft_pack_kernel<T>, grid, dim3(256), 0, st, fmap1, reinterpret_cast<T*>(pk + pl.f1), HW);
-    hipLaunchKernelGGL(raft_pack_kernel<T>, grid, dim3(256), 0, st, fmap2, reinterpret_cast<T*>(pk + pl.lev[0]), HW);
+    cl_pack<RC_D>(st, d->N, RC_D, d->H * d->W, RC_D, ClIdentity{}, fmap1, reinterpret_cast<T*>(pk + pl.f1));
+    cl_pack<RC_D>(st, d->N, RC_D, d->H * d->W, RC_D, ClIdentity{}, fmap2, reinterpret_cast<T*>(pk + pl.lev[0]));
     for (int l = 1; l < d->levels; ++l) {
         const long long chunks = (long long)d->N * pl.Hl[l] * pl.Wl[l] * (RC_D / 8);
         hipLaunchKernelGGL(raft_pool_kernel<T>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
@@ -346,9 +319,7 @@ int vsr_raft_corr_pyramid_bwd(const VsrRaftCorrDesc* d, void* gacc, size_t gacc_
     if (gacc_bytes < ga.total) return VSR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* gb = reinterpret_cast<char*>(gacc);
-    const int HW = d->H * d->W;
-    const dim3 grid(cdiv(HW, RC_PT), d->N);
-    if (dfmap1) hipLaunchKernelGGL(raft_unpack_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float*>(gb + ga.f1), dfmap1, HW);
+    if (dfmap1) cl_unpack<RC_D>(st, d->N, RC_D, d->H * d->W, RC_D, ClIdentity{}, reinterpret_cast<const float*>(gb + ga.f1), dfmap1);
     if (dfmap2) {
         for (int l = d->levels - 1; l >= 1; --l) {
             const long long quads = (long long)d->N * ga.Hl[l - 1] * ga.Wl[l - 1] * (RC_D / 4);
@@ -356,7 +327,7 @@ int vsr_raft_corr_pyramid_bwd(const VsrRaftCorrDesc* d, void* gacc, size_t gacc_
                                reinterpret_cast<float*>(gb + ga.lev[l - 1]), reinterpret_cast<const float*>(gb + ga.lev[l]), ga.Hl[l - 1],
                                ga.Wl[l - 1], ga.Hl[l], ga.Wl[l], quads);
         }
-        hipLaunchKernelGGL(raft_unpack_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float*>(gb + ga.lev[0]), dfmap2, HW);
+        cl_unpack<RC_D>(st, d->N, RC_D, d->H * d->W, RC_D, ClIdentity{}, reinterpret_cast<const float*>(gb + ga.lev[0]), dfmap2);
     }
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;

@@ -27,6 +27,7 @@
 // lane without an output pixel reads the staged tile only (every staged index is inside the tile by construction) and stores
 // nothing.
 #include "elt.h"
+#include "cl_stage.h"
 #include "host.h"
 #include "../../include/vsrlab_spatial_corr.h"
 
@@ -35,7 +36,6 @@ namespace {
 constexpr int SC_TY = 8, SC_TX = 32;    // pixels per workgroup: outputs (forward, d in1), in2 pixels (d in2)
 constexpr int SC_PMAX = 9;              // patch size per axis
 constexpr int SC_SMAX = 2, SC_DMAX = 2; // stride, dilation_patch
-constexpr int SC_PT = 32;               // pixels and channels per pack tile
 // the largest staged tiles (stride 2, dilation 2, patch 9), the fixed LDS row pitch and the 256-thread staging slots of each
 // tiling: _O by output pixel (forward, d in1), _I by in2 pixel (d in2)
 constexpr int SC_RH_O = (SC_TY - 1) * SC_SMAX + (SC_PMAX - 1) * SC_DMAX + 1, SC_PITCH_O = (SC_TX - 1) * SC_SMAX + (SC_PMAX - 1) * SC_DMAX + 1;
@@ -304,21 +304,6 @@ __global__ __launch_bounds__(256) void sc_bwd2_kernel(ScArgs a) {
     }
 }
 
-// ---- pack -----------------------------------------------------------------------------------------------------------------
-// planar fp32 (N, C, HW) -> pixel-major [N][HW][Cp] of T, channels C .. Cp - 1 zero; a tile is 32 pixels x 32 channels
-template <typename T>
-__global__ __launch_bounds__(256) void sc_pack_kernel(const float* x, T* dst, int HW, int C, int Cp) {
-    __shared__ float tile[SC_PT][SC_PT + 1];
-    const int n = blockIdx.z, p0 = blockIdx.x * SC_PT, c0 = blockIdx.y * SC_PT, t = threadIdx.x, px = t & 31;
-    for (int c = t >> 5; c < SC_PT; c += 8)
-        tile[px][c] = (p0 + px < HW && c0 + c < C) ? x[((long long)n * C + c0 + c) * HW + p0 + px] : 0.f;
-    __syncthreads();
-    for (int i = t; i < SC_PT * SC_PT; i += 256) {
-        const int q = i / SC_PT, c = i % SC_PT;
-        if (p0 + q < HW && c0 + c < Cp) dst[((long long)n * HW + p0 + q) * Cp + c0 + c] = (T)tile[q][c];
-    }
-}
-
 // ---- host -----------------------------------------------------------------------------------------------------------------
 struct ScPlan {
     int Cp, Ho, Wo, mh, mw;
@@ -368,11 +353,9 @@ unsigned sc_tile_by_in2(ScArgs& a) {
     return (unsigned)(a.tiles_x * cdiv(a.H, SC_TY));
 }
 
-template <typename T>
+template <typename T>   // cl_stage.h in 32-channel tiles: C reaches 65536
 void sc_pack(const VsrSpatialCorrDesc* d, const ScPlan& pl, const float* x, const void* dst, hipStream_t st) {
-    const int HW = d->H * d->W;
-    hipLaunchKernelGGL(sc_pack_kernel<T>, dim3(cdiv(HW, SC_PT), cdiv(pl.Cp, SC_PT), d->N), dim3(256), 0, st, x,
-                       reinterpret_cast<T*>(const_cast<void*>(dst)), HW, d->C, pl.Cp);
+    cl_pack<32>(st, d->N, d->C, d->H * d->W, pl.Cp, ClIdentity{}, x, reinterpret_cast<T*>(const_cast<void*>(dst)));
 }
 
 // A grid of `wgs` workgroups that leaves compute units idle is multiplied by blockIdx.z: `parts` independent units of work (patch

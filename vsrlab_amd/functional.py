@@ -919,6 +919,17 @@ def _tap_numels(n: int, h: int, w: int):
     return out
 
 
+def _backward_once(ctx, op: str, has_gradient: bool = True, noun: Optional[str] = None) -> None:
+    """What the backward of an op that keeps its gradient state in a workspace refuses: a double backward, a second backward,
+    and a backward through a forward that kept nothing for one.  `noun`: the op in words, where the messages use them."""
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"vsrlab_amd: {op} has no double backward (create_graph=True is not supported)")
+    if ctx.backward_done:
+        raise RuntimeError(f"vsrlab_amd: trying to backward through {f'the {noun}' if noun else op} a second time")
+    if not has_gradient:
+        raise RuntimeError(f"vsrlab_amd: backward through a {noun or op} that ran without a gradient")
+
+
 class _PerceptualFn(torch.autograd.Function):
     """loss = weight * sum_k LAYER_WEIGHTS[k] * mean|f_k(sr) - f_k(hr)|.  d loss / d sr is computed during the forward (one
     engine call per chunk of images) and is all the backward keeps; hr gets no gradient."""
@@ -957,12 +968,7 @@ class _PerceptualFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if torch.is_grad_enabled():
-            raise RuntimeError("vsrlab_amd: perceptual_loss has no double backward (create_graph=True is not supported)")
-        if ctx.backward_done:
-            raise RuntimeError("vsrlab_amd: trying to backward through the perceptual loss a second time")
-        if ctx.dsr is None:
-            raise RuntimeError("vsrlab_amd: backward through a perceptual loss that ran without a gradient")
+        _backward_once(ctx, "perceptual_loss", ctx.dsr is not None, noun="perceptual loss")
         dsr, ctx.dsr, ctx.backward_done = ctx.dsr, None, True
         return (g * dsr).to(ctx.sr_dtype), None, None, None, None, None, None, *([None] * 32)
 
@@ -1308,12 +1314,7 @@ class _DeformConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        if torch.is_grad_enabled():
-            raise RuntimeError("vsrlab_amd: deform_conv2d has no double backward (create_graph=True is not supported)")
-        if ctx.backward_done:
-            raise RuntimeError("vsrlab_amd: trying to backward through deform_conv2d a second time")
-        if not ctx.need_bwd:
-            raise RuntimeError("vsrlab_amd: backward through a deform_conv2d that ran without a gradient")
+        _backward_once(ctx, "deform_conv2d", ctx.need_bwd)
         lib = _lib.load()
         (x32, om32, mask32, flow32, w32), ctx.saved, ctx.backward_done = ctx.saved, None, True
         desc = ctx.desc
@@ -1507,10 +1508,7 @@ class _RaftPyramidFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gtoken):
-        if torch.is_grad_enabled():
-            raise RuntimeError("vsrlab_amd: raft_corr_pyramid has no double backward (create_graph=True is not supported)")
-        if ctx.backward_done:
-            raise RuntimeError("vsrlab_amd: trying to backward through raft_corr_pyramid a second time")
+        _backward_once(ctx, "raft_corr_pyramid")
         ctx.backward_done = True
         h = ctx.handle
         gacc, h.gacc = h.gacc, None
@@ -1544,12 +1542,7 @@ class _RaftLookupFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        if torch.is_grad_enabled():
-            raise RuntimeError("vsrlab_amd: raft_corr_lookup has no double backward (create_graph=True is not supported)")
-        if ctx.backward_done:
-            raise RuntimeError("vsrlab_amd: trying to backward through raft_corr_lookup a second time")
-        if ctx.coords is None:
-            raise RuntimeError("vsrlab_amd: backward through a raft_corr_lookup that ran without a gradient")
+        _backward_once(ctx, "raft_corr_lookup", ctx.coords is not None)
         lib = _lib.load()
         h = ctx.handle
         c32, ctx.coords, ctx.backward_done = ctx.coords, None, True
@@ -1645,12 +1638,7 @@ class _SpatialCorrFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        if torch.is_grad_enabled():
-            raise RuntimeError("vsrlab_amd: spatial_correlation has no double backward (create_graph=True is not supported)")
-        if ctx.backward_done:
-            raise RuntimeError("vsrlab_amd: trying to backward through spatial_correlation a second time")
-        if ctx.saved is None:
-            raise RuntimeError("vsrlab_amd: backward through a spatial_correlation that ran without a gradient")
+        _backward_once(ctx, "spatial_correlation", ctx.saved is not None)
         (a, b), ctx.saved, ctx.backward_done = ctx.saved, None, True
         gout = _f32c(gout)
         need = ctx.needs_input_grad

@@ -60,6 +60,12 @@ class SpatialCorrDesc(ctypes.Structure):
                                      "dtype")] + [("scale", c_float)]
 
 
+class JpegDesc(ctypes.Structure):
+    """struct VsrJpegDesc (include/vsrlab_jpeg.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "H", "W", "quality", "x_dtype", "y_dtype")] + \
+               [("x_stride", c_longlong * 4), ("y_stride", c_longlong * 4)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -172,8 +178,34 @@ SPATIAL_CORR_SIGNATURES = {
 }
 SPATIAL_CORR_EXPORTS = tuple(SPATIAL_CORR_SIGNATURES)
 
+# libvsrlab_jpeg.so (include/vsrlab_jpeg.h): the JPEG round trip, a library of its own for the same reason
+JPEG_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_jpeg.so")
+JPEG_SIGNATURES = {
+    "vsr_jpeg_workspace_bytes": (c_size_t, [ctypes.POINTER(JpegDesc)]),
+    "vsr_jpeg_fwd": (c_int, [ctypes.POINTER(JpegDesc), _P, _P, _P, c_size_t, _P]),
+}
+JPEG_EXPORTS = tuple(JPEG_SIGNATURES)
+
 _lib = None
 _spatial_corr_lib = None
+_jpeg_lib = None
+
+
+def load_jpeg():
+    """Load libvsrlab_jpeg.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
+    global _jpeg_lib
+    if _jpeg_lib is None:
+        if not os.path.exists(JPEG_LIB_PATH):
+            raise RuntimeError(
+                f"vsrlab_amd: HIP library not built ({JPEG_LIB_PATH} missing). Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
+        lib = ctypes.CDLL(JPEG_LIB_PATH)
+        for name, (res, args) in JPEG_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _jpeg_lib = lib
+    return _jpeg_lib
 
 
 def load_spatial_corr():

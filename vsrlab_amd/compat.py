@@ -19,7 +19,7 @@ def install_as_vsrlab(force: bool = False) -> None:
                 "vsr.models.RealBasicVSR.modules.basicvsr", "vsr.models.RealBasicVSR.modules.spynet",
                 "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.modules",
                 "vsr.models.VRT.modules.spynet", "vsr.models.VRT.modules.window_attention", "vsr.models.VRT.modules.tmsa", "vsr.models.VRT.modules.deform_conv",
-                "core.utils", "core.metrics", "train_gan", "optical_flow",
+                "core.utils", "core.metrics", "core.augmentations", "train_gan", "optical_flow",
                 "optical_flow.models", "optical_flow.models.spynet", "optical_flow.models.raft", "optical_flow.models.raft.raft",
                 "optical_flow.models.raft.corr", "optical_flow.models.raft.extractor", "optical_flow.models.raft.update",
                 "optical_flow.models.raft.utils", "optical_flow.models.irr", "optical_flow.models.irr.pwc_modules"):

@@ -66,6 +66,11 @@ class JpegDesc(ctypes.Structure):
                [("x_stride", c_longlong * 4), ("y_stride", c_longlong * 4)]
 
 
+class WarpTapsDesc(ctypes.Structure):
+    """struct VsrWarpTapsDesc (include/vsrlab_warp_taps.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "D", "C", "H", "W", "taps", "border", "dtype")] + [("x_nstride", c_longlong)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -186,9 +191,37 @@ JPEG_SIGNATURES = {
 }
 JPEG_EXPORTS = tuple(JPEG_SIGNATURES)
 
+# libvsrlab_warp_taps.so (include/vsrlab_warp_taps.h): the integer-tap warps ('nearest', 'nearest4') and VRT's aligned input, likewise
+WARP_TAPS_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_warp_taps.so")
+WARP_TAPS_SIGNATURES = {
+    "vsr_warp_taps_fwd": (c_int, [ctypes.POINTER(WarpTapsDesc), _P, _P, _P, _P]),
+    "vsr_warp_taps_bwd": (c_int, [ctypes.POINTER(WarpTapsDesc), _P, _P, _P, _P, _P]),
+    "vsr_warp_taps_clip_fwd": (c_int, [ctypes.POINTER(WarpTapsDesc), _P, _P, _P, _P, _P]),
+    "vsr_warp_taps_clip_bwd": (c_int, [ctypes.POINTER(WarpTapsDesc), _P, _P, _P, _P, _P, _P]),
+}
+WARP_TAPS_EXPORTS = tuple(WARP_TAPS_SIGNATURES)
+
 _lib = None
 _spatial_corr_lib = None
 _jpeg_lib = None
+_warp_taps_lib = None
+
+
+def load_warp_taps():
+    """Load libvsrlab_warp_taps.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
+    global _warp_taps_lib
+    if _warp_taps_lib is None:
+        if not os.path.exists(WARP_TAPS_LIB_PATH):
+            raise RuntimeError(
+                f"vsrlab_amd: HIP library not built ({WARP_TAPS_LIB_PATH} missing). Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
+        lib = ctypes.CDLL(WARP_TAPS_LIB_PATH)
+        for name, (res, args) in WARP_TAPS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _warp_taps_lib = lib
+    return _warp_taps_lib
 
 
 def load_jpeg():

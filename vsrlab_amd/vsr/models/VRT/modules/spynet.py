@@ -13,7 +13,11 @@ import torch.nn as nn
 from ..... import functional as VF
 
 pylogger = logging.getLogger(__name__)
-flow_warp = VF.flow_warp
+
+
+def flow_warp(x, flow, interp_mode='bilinear', padding_mode='zeros', align_corners=True):
+    """The reference's signature (:11): ``interp_mode`` 'bilinear', 'nearest' or 'nearest4'; see ``functional.flow_warp``."""
+    return VF.flow_warp(x, flow, interp_mode, padding_mode, align_corners)
 
 
 class BasicModule(nn.Module):

@@ -1029,7 +1029,8 @@ def test_spynet_7x7_layers_on_the_persistent_kernels(shape):
     weights, tap pairs for the 16-channel layers), bf16 build, through ConvReLU's per-op entry: against the same convolution of
     the bf16-rounded operands in fp32 (torch on the GPU; what differs is the summation order and the output's rounding to bf16:
     2^-8 relative), on ragged sizes from a single partial tile to several tiles per workgroup (4 x 200 x 330 = 1100 tiles on
-    256 workgroups: the weight ring wraps and both tile buffers are re-used), and bit-identical on a repeat."""
+    256 workgroups: the weight ring wraps and both tile buffers are re-used), and bit-identical on a repeat.  Every launch of these
+    layers against fp64, element by element, down to 1 x 1 images: tests/test_spynet_gpu.py (test_conv)."""
     dev = _gpu()
     from vsrlab_amd import functional as VF
     n, h, w = shape
@@ -1312,10 +1313,13 @@ def test_parity_suite_on_the_diet_arena_in_a_subprocess():
 @pytest.mark.parametrize("shape", [(2, 24, 40), (3, 72, 200)])
 def test_spynet_7x7_weight_gradients_on_the_producer_consumer_kernel(shape):
     """Weight / bias / input gradients of the five SPyNet layer shapes, bf16 build, through ConvReLU's autograd (vsr_conv_layer_bwd ->
-    wgrad7x7_pc.hip: all seven kernel rows in one launch, 7 x G workgroups; the data gradient stays on the generic kernel): against
+    wgrad7x7_pc.hip: all seven kernel rows in one launch, 7 x G workgroups; the data gradient is a 7x7 launch with one pixel-major
+    source, no residual and at most a ReLU mask, which vsr_launch_conv sends to conv7x7_persist.hip as well -- C7<32,1>, C7<64,2>,
+    C7<32,4>, C7<16,2>, C7<16,1>, with the q_relu_mask arm where the layer's input is an activation): against
     torch autograd of the same convolution on the bf16-rounded operands (the engine also rounds the masked cotangent to bf16:
     1e-2 relative L2), from one tile per workgroup to several (3 x 72 x 200 = 189 tiles on 32 workgroups per kernel row: both
-    buffer sets re-used), bit-identical on a repeat."""
+    buffer sets re-used), bit-identical on a repeat.  The 1e-2 norm does not see a lost column or border tap: every launch against fp64,
+    element by element, and exact-grid inputs at this size: tests/test_spynet_gpu.py (test_dgrad, test_wgrad)."""
     dev = _gpu()
     from vsrlab_amd import functional as VF
     n, h, w = shape

@@ -209,7 +209,8 @@ def _exported_vsr_symbols(path):
 def test_the_hooks_are_additions_to_an_unchanged_abi():
     """The library's exported `vsr_` symbols, enumerated from its dynamic symbol table: before the hooks it exported 74 -- the 67 of
     include/vsrlab_hip.h (= EXPORTS) and 7 vsr_debug_* entries (OTHER_DEBUG_EXPORTS) -- and now exactly those plus the 7
-    reconstruction-tail hooks (81) and the 7 propagation-trunk hooks (88), by name: nothing else, nothing missing.  The ABI number stays."""
+    reconstruction-tail hooks (81), the 7 propagation-trunk hooks (88) and the 7 SPyNet hooks (95), by name: nothing else, nothing missing.
+    The ABI number stays."""
     L, lib = _lib()
     import os
     import re
@@ -218,12 +219,13 @@ def test_the_hooks_are_additions_to_an_unchanged_abi():
     assert declared == set(L.EXPORTS) and len(L.EXPORTS) == 67 and lib.vsr_abi_version() == 4
     tail = {"vsr_debug_tail_" + k for k in ("last2_fwd", "last2_dgrad", "planar_c64", "last2_wgrad", "conv_unshuffle", "ps_dgrad", "ps_wgrads")}
     trunk = {"vsr_debug_trunk_" + k for k in ("conv", "stem", "stem_dgrad", "point", "wgrad_cc", "stem_wgrads", "chain")}
-    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk and len(tail | trunk) == 14
+    spy = {"vsr_debug_spy_" + k for k in ("conv", "dgrad", "wgrad", "prepare", "prepare_bwd", "dres", "planar")}
+    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk | spy and len(tail | trunk | spy) == 21
     assert not set(L.DEBUG_SIGNATURES) & declared and not set(L.DEBUG_SIGNATURES) & set(L.OTHER_DEBUG_EXPORTS)
     got = _exported_vsr_symbols(L.LIB_PATH)
     before = set(L.EXPORTS) | set(L.OTHER_DEBUG_EXPORTS)
     assert got - set(L.DEBUG_SIGNATURES) == before, (sorted(got - set(L.DEBUG_SIGNATURES) - before), sorted(before - got))
-    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7
+    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7 + 7
     for name in L.DEBUG_SIGNATURES:
         assert getattr(lib, name).argtypes == L.DEBUG_SIGNATURES[name][1]
 

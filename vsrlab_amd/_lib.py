@@ -171,6 +171,14 @@ DEBUG_SIGNATURES = {
     "vsr_debug_trunk_wgrad_cc": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "vsr_debug_trunk_stem_wgrads": (c_int, [c_int, c_int, c_int, _P, _LL, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, _P]),
     "vsr_debug_trunk_chain": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    # csrc/spynet_hooks.hip (dtype, layer j first for the three 7x7 entries; vsr_debug_spy_planar: op first, `planes` a long long)
+    "vsr_debug_spy_conv": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_dgrad": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_wgrad": (c_int, [c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_prepare": (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_prepare_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_dres": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_spy_planar": (c_int, [c_int, _P, _P, _P, _P, _P, _LL, c_int, c_int, c_int, c_int, _P]),
 }
 
 # libvsrlab_spatial_corr.so (include/vsrlab_spatial_corr.h): the local correlation, a library of its own -- the symbols that

@@ -372,7 +372,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(const ConvArgs a) {
                         const Vec4<T> m = *reinterpret_cast<const Vec4<T>*>(aux + (co >> 3) * 256 + (co & 7));
                         const float neg = a.mask_mode == MASK_LEAKY ? vsr_slope(a.leaky_slope) : 0.f;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] *= (to_f(m.v[j]) > 0.f ? 1.f : neg);
+                        for (int j = 0; j < 4; ++j)      // ReLU': +0 where masked, as the persistent kernels store (a product with 0 keeps v's sign: -0)
+                            v[j] = to_f(m.v[j]) > 0.f ? v[j] : (a.mask_mode == MASK_LEAKY ? v[j] * neg : 0.f);
                     }
                     Vec4<T> o;
 #pragma unroll

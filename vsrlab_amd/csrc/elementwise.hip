@@ -16,6 +16,55 @@ __device__ __forceinline__ float warp_coord(float base, float flow, int dim) {
     return (g + 1.0f) * 0.5f * (float)(dim - 1);
 }
 
+// The bilinear sample of flow_warp at pixel (x, y): top-left tap (x0, y0) and the weights of its two columns and two rows.
+// padding_mode='border' (grid_sample): the coordinate is clamped to the image; a clamped coordinate has no gradient w.r.t. the flow
+// (ATen clip_coordinates_set_grad).  Two conventions of "was clamped" are in use; they differ exactly where a coordinate lands on the
+// first or last pixel centre:
+//   GRAD_CLOSED  the gradient is kept on 0 <= p <= dim - 1: in_x / in_y                       (warp_bwd_flow_kernel)
+//   GRAD_OPEN    it is zeroed at p <= 0 and at p >= dim - 1, as ATen does: grad_gate_open()    (spynet_prepare_bwd_kernel)
+// and three tap policies:
+//   TEST   zeros padding: each of the four taps is tested against the image: warp_tap() + TAP_IN_IMAGE
+//   CLAMP  border, forward: the second tap's index is clamped into the image, its weight is then 0     (spynet_prepare_kernel)
+//   SKIP   border, adjoint: a second tap outside the image is skipped                                 (spynet_prepare_bwd_kernel)
+struct WarpSample {
+    int x0, y0;
+    float wx0, wx1, wy0, wy1;
+    float px, py;                  // the position before the border clamp
+    bool in_x, in_y;
+};
+// floor, int cast and weights of a sample position whose floor an int can hold
+__device__ __forceinline__ void warp_sample_at(float px, float py, WarpSample& s) {
+    const float fx0 = floorf(px), fy0 = floorf(py);
+    s.x0 = (int)fx0; s.y0 = (int)fy0;
+    s.wx1 = px - fx0; s.wy1 = py - fy0; s.wx0 = 1.f - s.wx1; s.wy0 = 1.f - s.wy1;
+}
+// ... which is for the caller to test where the flow is arbitrary (warp_bwd_far_kernel): the guard is what keeps the conversion defined
+__device__ __forceinline__ bool warp_floor_fits(float px, float py) {
+    return !(fabsf(floorf(px)) > 1e9f || fabsf(floorf(py)) > 1e9f);
+}
+__device__ __forceinline__ WarpSample warp_sample(int x, int y, float flow_x, float flow_y, int H, int W, int border) {
+    WarpSample s;
+    float px = warp_coord((float)x, flow_x, W);
+    float py = warp_coord((float)y, flow_y, H);
+    s.px = px; s.py = py;
+    s.in_x = !border || (px >= 0.f && px <= (float)(W - 1)); s.in_y = !border || (py >= 0.f && py <= (float)(H - 1));
+    if (border) { px = fminf(fmaxf(px, 0.f), (float)(W - 1)); py = fminf(fmaxf(py, 0.f), (float)(H - 1)); }
+    warp_sample_at(px, py, s);
+    return s;
+}
+__device__ __forceinline__ float grad_gate_open(float p, int dim) { return (p <= 0.f || p >= (float)(dim - 1)) ? 0.f : 1.f; }
+
+// Tap t = 0..3 of a sample, (x0 + (t & 1), y0 + (t >> 1)), with its weight (x weight) * (y weight).  The in-image test is a macro: as a
+// function hipcc merges the four taps' tests into fewer branches, another kernel than the one that was measured.
+struct WarpTap { int xi, yi; float wgt; };
+__device__ __forceinline__ WarpTap warp_tap(const WarpSample& s, int t) {
+    WarpTap p;
+    p.xi = s.x0 + (t & 1); p.yi = s.y0 + (t >> 1);
+    p.wgt = ((t & 1) ? s.wx1 : s.wx0) * ((t >> 1) ? s.wy1 : s.wy0);
+    return p;
+}
+#define TAP_IN_IMAGE(p, H, W) ((p).xi >= 0 && (p).xi < (W) && (p).yi >= 0 && (p).yi < (H))
+
 // out[n,y,x,:] = bilinear(in[n], (x+fx, y+fy)), zeros padding (each out-of-image tap contributes 0).
 template <typename T>
 __global__ void warp_fwd_kernel(const T* __restrict__ in, const float* __restrict__ flow, T* __restrict__ out,
@@ -30,29 +79,19 @@ __global__ void warp_fwd_kernel(const T* __restrict__ in, const float* __restric
         const int y = (int)((pix / W) % H);
         const int n = (int)(pix / ((long long)W * H));
         const float* fp = flow + (long long)n * flow_nstride + (long long)y * W + x;
-        float px = warp_coord((float)x, fp[0], W);
-        float py = warp_coord((float)y, fp[(long long)H * W], H);
-        // padding_mode='border' (grid_sample): the coordinate is clamped to the image; a clamped coordinate has no
-        // gradient w.r.t. the flow (ATen clip_coordinates_set_grad)
-        const bool in_x = !border || (px >= 0.f && px <= (float)(W - 1)), in_y = !border || (py >= 0.f && py <= (float)(H - 1));
-        if (border) { px = fminf(fmaxf(px, 0.f), (float)(W - 1)); py = fminf(fmaxf(py, 0.f), (float)(H - 1)); }
-        (void)in_x; (void)in_y;
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        const WarpSample s = warp_sample(x, y, fp[0], fp[(long long)H * W], H, W, border);
         float accv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) accv[j] = 0.f;
         const T* img = in + (long long)n * pm_image_elems(H, W, C);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
-            const float wgt = ((t & 1) ? wx1 : wx0) * ((t >> 1) ? wy1 : wy0);
-            if (xi >= 0 && xi < W && yi >= 0 && yi < H) {
+            const WarpTap p = warp_tap(s, t);
+            if (TAP_IN_IMAGE(p, H, W)) {
                 float f[8];
-                unpack8(*reinterpret_cast<const chunk_t*>(img + pm_off(yi, xi, c, W, C)), f);
+                unpack8(*reinterpret_cast<const chunk_t*>(img + pm_off(p.yi, p.xi, c, W, C)), f);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) accv[j] += f[j] * wgt;
+                for (int j = 0; j < 8; ++j) accv[j] += f[j] * p.wgt;
             }
         }
         chunk_t o;
@@ -75,23 +114,13 @@ __global__ void warp_bwd_kernel(const T* __restrict__ dout, const float* __restr
         const int y = (int)((pix / W) % H);
         const int n = (int)(pix / ((long long)W * H));
         const float* fp = flow + (long long)n * flow_nstride + (long long)y * W + x;
-        float px = warp_coord((float)x, fp[0], W);
-        float py = warp_coord((float)y, fp[(long long)H * W], H);
-        // padding_mode='border' (grid_sample): the coordinate is clamped to the image; a clamped coordinate has no
-        // gradient w.r.t. the flow (ATen clip_coordinates_set_grad)
-        const bool in_x = !border || (px >= 0.f && px <= (float)(W - 1)), in_y = !border || (py >= 0.f && py <= (float)(H - 1));
-        if (border) { px = fminf(fmaxf(px, 0.f), (float)(W - 1)); py = fminf(fmaxf(py, 0.f), (float)(H - 1)); }
-        (void)in_x; (void)in_y;
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        const WarpSample s = warp_sample(x, y, fp[0], fp[(long long)H * W], H, W, border);
         const float g = (float)dout[(long long)n * pm_image_elems(H, W, C) + pm_off(y, x, c >> 3, W, C) + (c & 7)];
         float* img = dacc + (long long)n * H * W * C;              // the fp32 accumulator stays plain [N][H][W][C]: 256-byte atomics
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
-            const float wgt = ((t & 1) ? wx1 : wx0) * ((t >> 1) ? wy1 : wy0);
-            if (xi >= 0 && xi < W && yi >= 0 && yi < H) atomicAdd(img + ((long long)yi * W + xi) * C + c, g * wgt);
+            const WarpTap p = warp_tap(s, t);
+            if (TAP_IN_IMAGE(p, H, W)) atomicAdd(img + ((long long)p.yi * W + p.xi) * C + c, g * p.wgt);
         }
     }
 }
@@ -158,7 +187,8 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const T* __restric
         pos[i] = p;
     }
     __syncthreads();
-    {   // phase 1: hits of destination pixel tid
+    {   // phase 1: hits of destination pixel tid.  (The hit test is written out here and in the rescan below: every helper form of it moved
+        // this kernel's time, profiles/warp_sample_isa.md.)
         const int dy = tid >> 5, dx = tid & 31;
         const int yi = ty0 + dy, xi = tx0 + dx;
         int cnt = 0;
@@ -259,33 +289,30 @@ __global__ void warp_bwd_far_kernel(const T* __restrict__ dout, const float* __r
         }
         unsigned long long todo = __ballot(mine < total && flow_is_far(mfx, mfy));
         while (todo) {
-        const int b = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const long long pix = base + b;
-        const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
-        const float fx = __shfl(mfx, b, 64), fy = __shfl(mfy, b, 64);
-        const int c = threadIdx.x & 63;
-        if (c == 0) atomicAdd(far_count, 1);
-        if (c >= C) continue;                           // C < 64: lanes C..63 have no channel
-        const float px = warp_coord((float)x, fx, W), py = warp_coord((float)y, fy, H);
-        if (!(px == px && py == py)) continue;
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        if (fabsf(fx0) > 1e9f || fabsf(fy0) > 1e9f) continue;
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-        const float g = (float)dout[(long long)n * pm_image_elems(H, W, C) + pm_off(y, x, c >> 3, W, C) + (c & 7)];
-        long long* imgp = S + (long long)n * H * W * C;
+            const int b = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const long long pix = base + b;
+            const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long long)W * H));
+            const float fx = __shfl(mfx, b, 64), fy = __shfl(mfy, b, 64);
+            const int c = threadIdx.x & 63;
+            if (c == 0) atomicAdd(far_count, 1);
+            if (c >= C) continue;                           // C < 64: lanes C..63 have no channel
+            const float px = warp_coord((float)x, fx, W), py = warp_coord((float)y, fy, H);
+            if (!(px == px && py == py) || !warp_floor_fits(px, py)) continue;
+            WarpSample s;
+            warp_sample_at(px, py, s);
+            const float g = (float)dout[(long long)n * pm_image_elems(H, W, C) + pm_off(y, x, c >> 3, W, C) + (c & 7)];
+            long long* imgp = S + (long long)n * H * W * C;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
-            const float wgt = ((t & 1) ? wx1 : wx0) * ((t >> 1) ? wy1 : wy0);
-            if (xi >= 0 && xi < W && yi >= 0 && yi < H) {
-                const float gw = g * wgt;
-                if (!(fabsf(gw) < 2.5e5f)) atomicOr(far_count, FAR_BAD);                          // NaN, Inf or beyond the fixed-point range
-                else atomicAdd(reinterpret_cast<unsigned long long*>(imgp + ((long long)yi * W + xi) * C + c),
-                               (unsigned long long)__double2ll_rn((double)gw * FAR_FX));       // two's complement: signed sums
+            for (int t = 0; t < 4; ++t) {
+                const WarpTap p = warp_tap(s, t);
+                if (TAP_IN_IMAGE(p, H, W)) {
+                    const float gw = g * p.wgt;
+                    if (!(fabsf(gw) < 2.5e5f)) atomicOr(far_count, FAR_BAD);                      // NaN, Inf or beyond the fixed-point range
+                    else atomicAdd(reinterpret_cast<unsigned long long*>(imgp + ((long long)p.yi * W + p.xi) * C + c),
+                                   (unsigned long long)__double2ll_rn((double)gw * FAR_FX));   // two's complement: signed sums
+                }
             }
-        }
         }
     }
 }
@@ -352,6 +379,27 @@ __device__ __forceinline__ void src_index(int d, float scale, int in_size, bool 
     l1 = s - (float)i0;
 }
 
+// The two-axis tap of the bilinear resizes: rows y0 / y1 and columns x0 / x1 of the source with the weights ly, lx of the second ones.
+struct ResizeTap { int y0, y1, x0, x1; float ly, lx; };
+__device__ __forceinline__ ResizeTap resize_tap(int y, float sy, int in_h, int x, float sx, int in_w, bool align) {
+    ResizeTap t;
+    src_index(y, sy, in_h, align, t.y0, t.y1, t.ly);
+    src_index(x, sx, in_w, align, t.x0, t.x1, t.lx);
+    return t;
+}
+// p: one plane of width w
+__device__ __forceinline__ float resize_read(const ResizeTap& t, const float* p, int w) {
+    return (1.f - t.ly) * ((1.f - t.lx) * p[t.y0 * w + t.x0] + t.lx * p[t.y0 * w + t.x1]) +
+           t.ly * ((1.f - t.lx) * p[t.y1 * w + t.x0] + t.lx * p[t.y1 * w + t.x1]);
+}
+// the adjoint of resize_read: p += resize^T(v)
+__device__ __forceinline__ void resize_scatter(const ResizeTap& t, float* p, int w, float v) {
+    atomicAdd(p + t.y0 * w + t.x0, v * (1.f - t.ly) * (1.f - t.lx));
+    atomicAdd(p + t.y0 * w + t.x1, v * (1.f - t.ly) * t.lx);
+    atomicAdd(p + t.y1 * w + t.x0, v * t.ly * (1.f - t.lx));
+    atomicAdd(p + t.y1 * w + t.x1, v * t.ly * t.lx);
+}
+
 // frames (F,3,h,w) -> ((bilinear resize to (hu,wu), align_corners=False) - mean) / std   spynet.py:72-80,40-41
 __global__ void resize_norm_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ mean,
                                    const float* __restrict__ std, int F, int h, int w, int hu, int wu) {
@@ -362,12 +410,7 @@ __global__ void resize_norm_kernel(const float* __restrict__ in, float* __restri
         const int y = (int)((idx / wu) % hu);
         const int c = (int)((idx / ((long long)wu * hu)) % 3);
         const long long f = idx / ((long long)wu * hu * 3);
-        int y0, y1, x0, x1; float ly, lx;
-        src_index(y, sy, h, false, y0, y1, ly);
-        src_index(x, sx, w, false, x0, x1, lx);
-        const float* p = in + (f * 3 + c) * (long long)h * w;
-        const float v = (1.f - ly) * ((1.f - lx) * p[y0 * w + x0] + lx * p[y0 * w + x1]) +
-                        ly * ((1.f - lx) * p[y1 * w + x0] + lx * p[y1 * w + x1]);
+        const float v = resize_read(resize_tap(y, sy, h, x, sx, w, false), in + (f * 3 + c) * (long long)h * w, w);
         out[idx] = (v - mean[c]) / std[c];
     }
 }
@@ -389,7 +432,8 @@ __global__ void avgpool2_kernel(const float* __restrict__ in, float* __restrict_
 //   flow_up = level 0 ? 0 : 2 * bilinear_x2(flow_prev, align_corners=True)
 //   x16[p] = [ref(3) | warp(supp, flow_up, border)(3) | flow_up(2) | 0 x 8]      pixel-major, 16 channels
 // Pair p of P = 2*n*(t-1): p < P/2 -> backward flow (ref = frame i, supp = i+1), else forward
-// (ref = frame i+1, supp = i)  (basicvsr.py:32-35).
+// (ref = frame i+1, supp = i)  (basicvsr.py:32-35).  The pair -> (fref, fsup) map is written out here and in spynet_prepare_bwd_kernel:
+// as a function hipcc compiles its two selects without the branch these kernels have (profiles/warp_sample_isa.md).
 template <typename T>
 __global__ void spynet_prepare_kernel(const float* __restrict__ frames, const float* __restrict__ flow_prev,
                                       float* __restrict__ flow_up, T* __restrict__ x16, int n, int t, int P, int pair_mode,
@@ -414,33 +458,23 @@ __global__ void spynet_prepare_kernel(const float* __restrict__ frames, const fl
         }
         float fu[2] = {0.f, 0.f};
         if (!level0) {
-            int y0, y1, x0, x1; float ly, lx;
-            src_index(y, sy, hp, true, y0, y1, ly);
-            src_index(x, sx, wp, true, x0, x1, lx);
+            const ResizeTap up = resize_tap(y, sy, hp, x, sx, wp, true);
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const float* fp = flow_prev + ((long long)p * 2 + c) * hp * wp;
-                fu[c] = 2.0f * ((1.f - ly) * ((1.f - lx) * fp[y0 * wp + x0] + lx * fp[y0 * wp + x1]) +
-                                ly * ((1.f - lx) * fp[y1 * wp + x0] + lx * fp[y1 * wp + x1]));
-            }
+            for (int c = 0; c < 2; ++c) fu[c] = 2.0f * resize_read(up, flow_prev + ((long long)p * 2 + c) * hp * wp, wp);
         }
         const long long hw = (long long)h * w;
         flow_up[((long long)p * 2 + 0) * hw + (long long)y * w + x] = fu[0];
         flow_up[((long long)p * 2 + 1) * hw + (long long)y * w + x] = fu[1];
-        // border-mode warp of the supporting frame
-        float px = warp_coord((float)x, fu[0], w), py = warp_coord((float)y, fu[1], h);
-        px = fminf(fmaxf(px, 0.f), (float)(w - 1));
-        py = fminf(fmaxf(py, 0.f), (float)(h - 1));
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const int x1 = x0 + 1 < w ? x0 + 1 : w - 1, y1 = y0 + 1 < h ? y0 + 1 : h - 1;   // weight of a clamped tap is 0
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        // border-mode warp of the supporting frame, CLAMP policy: the weight of a clamped tap is 0
+        const WarpSample s = warp_sample(x, y, fu[0], fu[1], h, w, 1);
+        const int x0 = s.x0, y0 = s.y0;
+        const int x1 = x0 + 1 < w ? x0 + 1 : w - 1, y1 = y0 + 1 < h ? y0 + 1 : h - 1;
         float v[8];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             v[c] = frames[((long long)fref * 3 + c) * hw + (long long)y * w + x];
             const float* sp = frames + ((long long)fsup * 3 + c) * hw;
-            v[3 + c] = wy0 * (wx0 * sp[y0 * w + x0] + wx1 * sp[y0 * w + x1]) + wy1 * (wx0 * sp[y1 * w + x0] + wx1 * sp[y1 * w + x1]);
+            v[3 + c] = s.wy0 * (s.wx0 * sp[y0 * w + x0] + s.wx1 * sp[y0 * w + x1]) + s.wy1 * (s.wx0 * sp[y1 * w + x0] + s.wx1 * sp[y1 * w + x1]);
         }
         v[6] = fu[0]; v[7] = fu[1];
         typename Elt<T>::chunk_t lo, hi;
@@ -462,12 +496,7 @@ __global__ void flow_out_kernel(const float* __restrict__ in, float* __restrict_
         const int y = (int)((idx / w) % h);
         const int c = (int)((idx / ((long long)w * h)) % 2);
         const long long p = idx / ((long long)w * h * 2);
-        int y0, y1, x0, x1; float ly, lx;
-        src_index(y, sy, hu, false, y0, y1, ly);
-        src_index(x, sx, wu, false, x0, x1, lx);
-        const float* ip = in + (p * 2 + c) * (long long)hu * wu;
-        const float v = (1.f - ly) * ((1.f - lx) * ip[y0 * wu + x0] + lx * ip[y0 * wu + x1]) +
-                        ly * ((1.f - lx) * ip[y1 * wu + x0] + lx * ip[y1 * wu + x1]);
+        const float v = resize_read(resize_tap(y, sy, hu, x, sx, wu, false), in + (p * 2 + c) * (long long)hu * wu, wu);
         out[idx] = v * (c == 0 ? (float)w / (float)wu : (float)h / (float)hu);
     }
 }
@@ -488,16 +517,7 @@ __global__ void warp_bwd_flow_kernel(const T* __restrict__ in, const T* __restri
         const int y = (int)((pix / W) % H);
         const int n = (int)(pix / ((long long)W * H));
         const float* fp = flow + (long long)n * flow_nstride + (long long)y * W + x;
-        float px = warp_coord((float)x, fp[0], W);
-        float py = warp_coord((float)y, fp[(long long)H * W], H);
-        // padding_mode='border' (grid_sample): the coordinate is clamped to the image; a clamped coordinate has no
-        // gradient w.r.t. the flow (ATen clip_coordinates_set_grad)
-        const bool in_x = !border || (px >= 0.f && px <= (float)(W - 1)), in_y = !border || (py >= 0.f && py <= (float)(H - 1));
-        if (border) { px = fminf(fmaxf(px, 0.f), (float)(W - 1)); py = fminf(fmaxf(py, 0.f), (float)(H - 1)); }
-        (void)in_x; (void)in_y;
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        const WarpSample s = warp_sample(x, y, fp[0], fp[(long long)H * W], H, W, border);
         const T* img = in + (long long)n * pm_image_elems(H, W, C);
         const T* dimg = dout + (long long)n * pm_image_elems(H, W, C);
         float gx = 0.f, gy = 0.f;
@@ -506,9 +526,9 @@ __global__ void warp_bwd_flow_kernel(const T* __restrict__ in, const T* __restri
             unpack8(*reinterpret_cast<const chunk_t*>(dimg + pm_off(y, x, c, W, C)), g);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
-                if (xi >= 0 && xi < W && yi >= 0 && yi < H) {
-                    unpack8(*reinterpret_cast<const chunk_t*>(img + pm_off(yi, xi, c, W, C)), v[t]);
+                const WarpTap p = warp_tap(s, t);
+                if (TAP_IN_IMAGE(p, H, W)) {
+                    unpack8(*reinterpret_cast<const chunk_t*>(img + pm_off(p.yi, p.xi, c, W, C)), v[t]);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[t][j] = 0.f;
@@ -516,13 +536,13 @@ __global__ void warp_bwd_flow_kernel(const T* __restrict__ in, const T* __restri
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                gx += g[j] * (wy0 * (v[1][j] - v[0][j]) + wy1 * (v[3][j] - v[2][j]));
-                gy += g[j] * (wx0 * (v[2][j] - v[0][j]) + wx1 * (v[3][j] - v[1][j]));
+                gx += g[j] * (s.wy0 * (v[1][j] - v[0][j]) + s.wy1 * (v[3][j] - v[2][j]));
+                gy += g[j] * (s.wx0 * (v[2][j] - v[0][j]) + s.wx1 * (v[3][j] - v[1][j]));
             }
         }
         float* dp = dflow + (long long)n * flow_nstride + (long long)y * W + x;
-        dp[0] = (W > 1 && in_x) ? gx : 0.f;
-        dp[(long long)H * W] = (H > 1 && in_y) ? gy : 0.f;
+        dp[0] = (W > 1 && s.in_x) ? gx : 0.f;                   // GRAD_CLOSED
+        dp[(long long)H * W] = (H > 1 && s.in_y) ? gy : 0.f;
     }
 }
 
@@ -584,17 +604,13 @@ __global__ void spynet_prepare_bwd_kernel(const T* __restrict__ dx16, const floa
         unpack8(*reinterpret_cast<const typename Elt<T>::chunk_t*>(dx16 + (long long)p * pm_image_elems(h, w, 16) + pm_off(y, x, 0, w, 16)), d);
         const float fu0 = flow_up ? flow_up[((long long)p * 2 + 0) * hw + (long long)y * w + x] : 0.f;   // level 0: flow_up = 0
         const float fu1 = flow_up ? flow_up[((long long)p * 2 + 1) * hw + (long long)y * w + x] : 0.f;
-        float px = warp_coord((float)x, fu0, w), py = warp_coord((float)y, fu1, h);
-        // border padding: clip_coordinates_set_grad (the gradient is 0 where the coordinate was clipped)
-        const float mx = (px <= 0.f || px >= (float)(w - 1)) ? 0.f : 1.f;
-        const float my = (py <= 0.f || py >= (float)(h - 1)) ? 0.f : 1.f;
-        px = fminf(fmaxf(px, 0.f), (float)(w - 1));
-        py = fminf(fmaxf(py, 0.f), (float)(h - 1));
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const int x0 = (int)fx0, y0 = (int)fy0;
+        // border-mode warp, GRAD_OPEN; SKIP policy: a second tap outside the image is not touched
+        const WarpSample s = warp_sample(x, y, fu0, fu1, h, w, 1);
+        const float mx = grad_gate_open(s.px, w), my = grad_gate_open(s.py, h);
+        const int x0 = s.x0, y0 = s.y0;
         const bool x1ok = x0 + 1 < w, y1ok = y0 + 1 < h;
         const int x1 = x1ok ? x0 + 1 : x0, y1 = y1ok ? y0 + 1 : y0;
-        const float wx1 = px - fx0, wy1 = py - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+        const float wx0 = s.wx0, wx1 = s.wx1, wy0 = s.wy0, wy1 = s.wy1;
         float gx = 0.f, gy = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -626,18 +642,9 @@ __global__ void spynet_prepare_bwd_kernel(const T* __restrict__ dx16, const floa
             g[0] += dflow_l[((long long)p * 2 + 0) * hw + (long long)y * w + x];
             g[1] += dflow_l[((long long)p * 2 + 1) * hw + (long long)y * w + x];
         }
-        int yy0, yy1, xx0, xx1; float ly, lx;
-        src_index(y, sy, hp, true, yy0, yy1, ly);
-        src_index(x, sx, wp, true, xx0, xx1, lx);
+        const ResizeTap up = resize_tap(y, sy, hp, x, sx, wp, true);
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            float* dp = dflow_prev + ((long long)p * 2 + c) * hp * wp;
-            const float v = 2.0f * g[c];
-            atomicAdd(dp + yy0 * wp + xx0, v * (1.f - ly) * (1.f - lx));
-            atomicAdd(dp + yy0 * wp + xx1, v * (1.f - ly) * lx);
-            atomicAdd(dp + yy1 * wp + xx0, v * ly * (1.f - lx));
-            atomicAdd(dp + yy1 * wp + xx1, v * ly * lx);
-        }
+        for (int c = 0; c < 2; ++c) resize_scatter(up, dflow_prev + ((long long)p * 2 + c) * hp * wp, wp, 2.0f * g[c]);
     }
 }
 
@@ -650,15 +657,8 @@ __global__ void flow_out_bwd_kernel(const float* __restrict__ dout, float* __res
         const int y = (int)((idx / w) % h);
         const int c = (int)((idx / ((long long)w * h)) % 2);
         const long long p = idx / ((long long)w * h * 2);
-        int y0, y1, x0, x1; float ly, lx;
-        src_index(y, sy, hu, false, y0, y1, ly);
-        src_index(x, sx, wu, false, x0, x1, lx);
-        float* ip = din + (p * 2 + c) * (long long)hu * wu;
-        const float v = dout[idx] * (c == 0 ? (float)w / (float)wu : (float)h / (float)hu);
-        atomicAdd(ip + y0 * wu + x0, v * (1.f - ly) * (1.f - lx));
-        atomicAdd(ip + y0 * wu + x1, v * (1.f - ly) * lx);
-        atomicAdd(ip + y1 * wu + x0, v * ly * (1.f - lx));
-        atomicAdd(ip + y1 * wu + x1, v * ly * lx);
+        resize_scatter(resize_tap(y, sy, hu, x, sx, wu, false), din + (p * 2 + c) * (long long)hu * wu, wu,
+                       dout[idx] * (c == 0 ? (float)w / (float)wu : (float)h / (float)hu));
     }
 }
 
@@ -684,15 +684,7 @@ __global__ void resize_norm_bwd_kernel(const float* __restrict__ dnorm, float* _
         const int y = (int)((idx / wu) % hu);
         const int c = (int)((idx / ((long long)wu * hu)) % 3);
         const long long f = idx / ((long long)wu * hu * 3);
-        int y0, y1, x0, x1; float ly, lx;
-        src_index(y, sy, h, false, y0, y1, ly);
-        src_index(x, sx, w, false, x0, x1, lx);
-        float* p = dframes + (f * 3 + c) * (long long)h * w;
-        const float v = dnorm[idx] / std[c];
-        atomicAdd(p + y0 * w + x0, v * (1.f - ly) * (1.f - lx));
-        atomicAdd(p + y0 * w + x1, v * (1.f - ly) * lx);
-        atomicAdd(p + y1 * w + x0, v * ly * (1.f - lx));
-        atomicAdd(p + y1 * w + x1, v * ly * lx);
+        resize_scatter(resize_tap(y, sy, h, x, sx, w, false), dframes + (f * 3 + c) * (long long)h * w, w, dnorm[idx] / std[c]);
     }
 }
 
@@ -747,6 +739,11 @@ __global__ void add_f32_kernel(const float* __restrict__ a, const float* __restr
 // OIHW fp32 -> packed T [tap][R][Cc] consumed by conv_mfma (A operand rows = R, K = Cc).
 //   mode 0 (forward):  dst[tap][r][c] = w[r*o_mul + o_add][i_off + c][tap]
 //   mode 1 (data grad): dst[tap][r][c] = w[c*o_mul + o_add][i_off + r][KK-1-tap]   (flipped taps, roles swapped)
+__device__ __forceinline__ float pack_element(const float* w, int tap, int r, int c, int KK, int I_total, int i_off, int o_mul, int o_add, int mode) {
+    if (mode == 0) return w[((long long)(r * o_mul + o_add) * I_total + i_off + c) * KK + tap];
+    return w[((long long)(c * o_mul + o_add) * I_total + i_off + r) * KK + (KK - 1 - tap)];
+}
+
 template <typename T>
 __global__ void pack_weights_kernel(const float* __restrict__ w, T* __restrict__ dst, int KK, int RP, int CPd,
                                     int r_real, int c_real, int I_total, int i_off, int o_mul, int o_add, int mode) {
@@ -755,10 +752,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, T* __restrict__
     if (idx >= total) return;
     const int c = idx % CPd, r = (idx / CPd) % RP, tap = idx / (CPd * RP);
     float v = 0.f;
-    if (r < r_real && c < c_real) {
-        if (mode == 0) v = w[((long long)(r * o_mul + o_add) * I_total + i_off + c) * KK + tap];
-        else v = w[((long long)(c * o_mul + o_add) * I_total + i_off + r) * KK + (KK - 1 - tap)];
-    }
+    if (r < r_real && c < c_real) v = pack_element(w, tap, r, c, KK, I_total, i_off, o_mul, o_add, mode);
     dst[idx] = (T)v;
 }
 
@@ -778,10 +772,7 @@ __global__ void pack_multi_kernel(const PackArgs a) {
     const int KK = d.KK, RP = d.RP, CPd = d.CPd;
     const int c = idx % CPd, r = (idx / CPd) % RP, tap = idx / (CPd * RP);
     float v = 0.f;
-    if (r < d.r_real && c < d.c_real) {
-        if (d.mode == 0) v = d.w[((long long)(r * d.o_mul + d.o_add) * d.I_total + d.i_off + c) * KK + tap];
-        else v = d.w[((long long)(c * d.o_mul + d.o_add) * d.I_total + d.i_off + r) * KK + (KK - 1 - tap)];
-    }
+    if (r < d.r_real && c < d.c_real) v = pack_element(d.w, tap, r, c, KK, d.I_total, d.i_off, d.o_mul, d.o_add, d.mode);
     if (d.dtype == VSR_BF16) reinterpret_cast<bf16_t*>(d.dst)[idx] = (bf16_t)v;
     else reinterpret_cast<float*>(d.dst)[idx] = v;
 }

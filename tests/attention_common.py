@@ -218,15 +218,16 @@ def host_pack(mask):
     return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
 
 
-def run_hip(c: Case, qkv, dout, bias, mask, dtype, dev, backward=True):
+def run_hip(c: Case, qkv, dout, bias, mask, dtype, dev, backward=True, lib=None):
     """One descriptor through vsr_window_attention_fwd / _bwd.  Every input is a view into a larger buffer whose surround is NaN, and
     so is everything inside an input that the descriptor does not name (q rows outside the queries, k / v rows outside the keys, dout
     outside its rows and channels, the mask outside its top-left block): a stray read shows as NaN in a result.  Every output sits in
     a sentinel-filled buffer, and whatever the descriptor does not name is compared with the sentinel bit for bit.
+    ``lib``: another build of the library, loaded with ctypes (tools/ab_attention.py); default: the package's own.
     Returns the same dict as ``attention_fp64`` (fp32 CPU tensors)."""
     from vsrlab_amd import _lib
     from vsrlab_amd import functional as VF
-    lib = _lib.load()
+    lib = _lib.load() if lib is None else lib
     tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
     nan = float("nan")
     H, hd, C = c.heads, c.hd, c.C

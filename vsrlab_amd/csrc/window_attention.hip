@@ -17,7 +17,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include "elt.h"
-#include "kernels.h"
+#include "host.h"
 #include "../../include/vsrlab_hip.h"
 
 namespace {
@@ -798,16 +798,18 @@ __global__ void mask_pack_kernel(const float* __restrict__ mask, unsigned* __res
     }
 }
 
-template <typename K>
-int launch_attn_p(K kern, VsrDevOnce& once, const AttnArgs& a, int waves, size_t lds, hipStream_t st) {
-    if (lds > 64 * 1024) { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(kern), (int)lds); if (rc != VSR_OK) return rc; }
+// KERN as a template argument: every kernel has the same function-pointer type, and each needs its own once-per-device flag
+template <void (*KERN)(const AttnArgs)>
+int launch_attn_p(const AttnArgs& a, int waves, size_t lds, hipStream_t st) {
+    static VsrDevOnce once;
+    if (lds > 64 * 1024) { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(KERN), (int)lds); if (rc != VSR_OK) return rc; }
     // ~2048 resident threads per CU; one partition = 8 workgroups per head (one per XCD)
     const int per_cu = 2048 / (waves * 64);
     int pp = (vsr_num_cus() * per_cu) / (8 * a.nH);
     const int need = (a.B + 7) / 8;
     if (pp > need) pp = need;
     if (pp < 1) pp = 1;
-    hipLaunchKernelGGL(kern, dim3(8 * a.nH * pp), dim3(waves * 64), lds, st, a);
+    hipLaunchKernelGGL(KERN, dim3(8 * a.nH * pp), dim3(waves * 64), lds, st, a);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
 }
@@ -830,10 +832,11 @@ __global__ void rpb_scatter_kernel(const float* __restrict__ ddense, const long 
     }
 }
 
-template <typename K>
-int launch_attn(K kern, VsrDevOnce& once, const AttnArgs& a, int blocks_x, int waves, size_t lds, hipStream_t st) {
-    if (lds > 64 * 1024) { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(kern), (int)lds); if (rc != VSR_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3(blocks_x, a.nH, a.B), dim3(waves * 64), lds, st, a);
+template <void (*KERN)(const AttnArgs)>
+int launch_attn(const AttnArgs& a, int blocks_x, int waves, size_t lds, hipStream_t st) {
+    static VsrDevOnce once;
+    if (lds > 64 * 1024) { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(KERN), (int)lds); if (rc != VSR_OK) return rc; }
+    hipLaunchKernelGGL(KERN, dim3(blocks_x, a.nH, a.B), dim3(waves * 64), lds, st, a);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
 }
@@ -843,7 +846,7 @@ bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) !=
 
 int check_args(const VsrAttnDesc* d, const void* qkv) {
     if (!d || !qkv) return VSR_ERR_BADARG;
-    if (d->dtype != VSR_F32 && d->dtype != VSR_BF16) return VSR_ERR_BADARG;
+    if (bad_dtype(d->dtype)) return VSR_ERR_BADARG;
     if (d->B < 1 || d->N < 1 || d->heads < 1 || d->head_dim < 1 || d->head_dim > HP) return VSR_ERR_UNSUPPORTED;
     if (d->Nq < 32 || (d->Nq & 31) || d->Nq > 16 * MAXT) return VSR_ERR_UNSUPPORTED;
     if (d->Nk != 64 && d->Nk != 128 && d->Nk != 192 && d->Nk != 256 && d->Nk != 384) return VSR_ERR_UNSUPPORTED;   // instantiated key counts
@@ -867,6 +870,55 @@ AttnArgs make_args(const VsrAttnDesc* d) {
     a.Cout = d->Cout; a.c_off = d->c_off; a.scale = d->scale; a.nW = d->nW > 0 ? d->nW : 1; a.Nm = d->Nm;
     a.mask_value = d->mask_value;
     return a;
+}
+
+// One pass of one element type: the persistent kernels for Nq == Nk in {64, 128} (wave count = Nk / 16), else the
+// per-(window, head) kernel instantiated for Nk
+#define ATTN_NT_CASES(X) X(4) X(8) X(12) X(16) X(24)
+inline bool persistent_shape(const VsrAttnDesc* d) { return d->Nq == d->Nk && (d->Nk == 128 || d->Nk == 64); }
+
+template <typename T>
+int attn_fwd(const VsrAttnDesc* d, const AttnArgs& a, hipStream_t st) {
+    if (persistent_shape(d)) {
+        const size_t l = (size_t)2 * (d->Nk * HP + HP * (d->Nk + 8)) * sizeof(T);
+        if (d->Nk == 128) return launch_attn_p<attn_fwd_p_kernel<T, 8, 8>>(a, 8, l, st);
+        return launch_attn_p<attn_fwd_p_kernel<T, 4, 4>>(a, 4, l, st);
+    }
+    const int wv = d->Nq / WQ < MAXW ? d->Nq / WQ : MAXW;
+    const size_t lds = ((size_t)d->Nk * HP + (size_t)HP * (d->Nk + 8)) * sizeof(T);
+#define X(NT_) if (d->Nk == 16 * NT_) return launch_attn<attn_fwd_kernel<T, NT_>>(a, 1, wv, lds, st);
+    ATTN_NT_CASES(X)
+#undef X
+    return VSR_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int attn_bwd(const VsrAttnDesc* d, AttnArgs& a, hipStream_t st) {
+    const size_t es = sizeof(T);
+    const size_t lds1 = ((size_t)2 * d->Nk * HP + (size_t)HP * (d->Nk + 8)) * es;
+    const int wq = d->Nq / WQ < MAXW ? d->Nq / WQ : MAXW, wk = d->Nk / WQ < MAXW ? d->Nk / WQ : MAXW;
+    const int qc = kv_chunk(d->Nq);
+    if (d->Nq % qc != 0) return VSR_ERR_UNSUPPORTED;
+    a.qc = qc;
+    const size_t lds2 = ((size_t)2 * qc * HP + (size_t)2 * HP * (qc + 8)) * es + (size_t)2 * qc * 4;
+    if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return VSR_ERR_UNSUPPORTED;
+    if (persistent_shape(d)) {
+        const int nn = d->Nk;
+        const size_t lq = (size_t)2 * (2 * nn * HP + HP * (nn + 8)) * es;
+        const size_t lk = (size_t)2 * (2 * nn * HP + 2 * HP * (nn + 8)) * es + (size_t)4 * nn * 4;
+        if (nn == 128) {
+            CK((launch_attn_p<attn_bwd_q_p_kernel<T, 8, 8>>(a, 8, lq, st)));
+            return launch_attn_p<attn_bwd_kv_p_kernel<T, 8, 8>>(a, 8, lk, st);
+        }
+        CK((launch_attn_p<attn_bwd_q_p_kernel<T, 4, 4>>(a, 4, lq, st)));
+        return launch_attn_p<attn_bwd_kv_p_kernel<T, 4, 4>>(a, 4, lk, st);
+    }
+    int rc = VSR_ERR_UNSUPPORTED;
+#define X(NT_) if (d->Nk == 16 * NT_) rc = launch_attn<attn_bwd_q_kernel<T, NT_>>(a, 1, wq, lds1, st);
+    ATTN_NT_CASES(X)
+#undef X
+    if (rc != VSR_OK) return rc;
+    return launch_attn<attn_bwd_kv_kernel<T>>(a, cdiv(d->Nk, WQ * wk), wk, lds2, st);
 }
 
 }  // namespace
@@ -920,30 +972,7 @@ int vsr_window_attention_fwd(const VsrAttnDesc* d, const void* qkv, const float*
     a.qkv = qkv; a.out = out; a.lse = lse; a.bias = bias;
     rc = set_mask(d, mask, a);
     if (rc != VSR_OK) return rc;
-    const int bx = 1, wv = d->Nq / WQ < MAXW ? d->Nq / WQ : MAXW;
-    const size_t es = d->dtype == VSR_BF16 ? 2 : 4;
-    const size_t lds = ((size_t)d->Nk * HP + (size_t)HP * (d->Nk + 8)) * es;
-    if (d->Nq == d->Nk && (d->Nk == 128 || d->Nk == 64)) {
-        static VsrDevOnce p1, p2, p3, p4;
-        if (d->Nk == 128) {
-            const size_t l = (size_t)2 * (128 * HP + HP * 136) * es;
-            if (d->dtype == VSR_BF16) return launch_attn_p(attn_fwd_p_kernel<bf16_t, 8, 8>, p1, a, 8, l, (hipStream_t)stream);
-            return launch_attn_p(attn_fwd_p_kernel<float, 8, 8>, p2, a, 8, l, (hipStream_t)stream);
-        }
-        const size_t l = (size_t)2 * (64 * HP + HP * 72) * es;
-        if (d->dtype == VSR_BF16) return launch_attn_p(attn_fwd_p_kernel<bf16_t, 4, 4>, p3, a, 4, l, (hipStream_t)stream);
-        return launch_attn_p(attn_fwd_p_kernel<float, 4, 4>, p4, a, 4, l, (hipStream_t)stream);
-    }
-#define ATTN_NT_CASES(X) X(4) X(8) X(12) X(16) X(24)
-#define X(NT_)                                                                                                        \
-    if (d->Nk == 16 * NT_) {                                                                                          \
-        static VsrDevOnce o1, o2;                                                                                     \
-        if (d->dtype == VSR_BF16) return launch_attn(attn_fwd_kernel<bf16_t, NT_>, o1, a, bx, wv, lds, (hipStream_t)stream); \
-        return launch_attn(attn_fwd_kernel<float, NT_>, o2, a, bx, wv, lds, (hipStream_t)stream);                        \
-    }
-    ATTN_NT_CASES(X)
-#undef X
-    return VSR_ERR_UNSUPPORTED;
+    return d->dtype == VSR_BF16 ? attn_fwd<bf16_t>(d, a, (hipStream_t)stream) : attn_fwd<float>(d, a, (hipStream_t)stream);
 }
 
 int vsr_window_attention_bwd(const VsrAttnDesc* d, const void* qkv, const float* bias, const float* mask, const void* dout, const float* lse,
@@ -956,46 +985,7 @@ int vsr_window_attention_bwd(const VsrAttnDesc* d, const void* qkv, const float*
     a.qkv = qkv; a.dout = dout; a.dqkv = dqkv; a.lse = const_cast<float*>(lse); a.delta = delta; a.bias = bias; a.dbias = dbias;
     rc = set_mask(d, mask, a);
     if (rc != VSR_OK) return rc;
-    const size_t es = d->dtype == VSR_BF16 ? 2 : 4;
-    hipStream_t st = (hipStream_t)stream;
-    static VsrDevOnce o2, o4;
-    const size_t lds1 = ((size_t)2 * d->Nk * HP + (size_t)HP * (d->Nk + 8)) * es;
-    const int wq = d->Nq / WQ < MAXW ? d->Nq / WQ : MAXW, wk = d->Nk / WQ < MAXW ? d->Nk / WQ : MAXW;
-    const int qc = kv_chunk(d->Nq);
-    if (d->Nq % qc != 0) return VSR_ERR_UNSUPPORTED;
-    a.qc = qc;
-    const size_t lds2 = ((size_t)2 * qc * HP + (size_t)2 * HP * (qc + 8)) * es + (size_t)2 * qc * 4;
-    if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return VSR_ERR_UNSUPPORTED;
-    if (d->Nq == d->Nk && (d->Nk == 128 || d->Nk == 64)) {
-        static VsrDevOnce p1, p2, p3, p4, p5, p6, p7, p8;
-        const int nn = d->Nk;
-        const size_t lq = (size_t)2 * (2 * nn * HP + HP * (nn + 8)) * es;
-        const size_t lk = (size_t)2 * (2 * nn * HP + 2 * HP * (nn + 8)) * es + (size_t)4 * nn * 4;
-        if (nn == 128) {
-            rc = d->dtype == VSR_BF16 ? launch_attn_p(attn_bwd_q_p_kernel<bf16_t, 8, 8>, p1, a, 8, lq, st)
-                                      : launch_attn_p(attn_bwd_q_p_kernel<float, 8, 8>, p2, a, 8, lq, st);
-            if (rc != VSR_OK) return rc;
-            return d->dtype == VSR_BF16 ? launch_attn_p(attn_bwd_kv_p_kernel<bf16_t, 8, 8>, p3, a, 8, lk, st)
-                                        : launch_attn_p(attn_bwd_kv_p_kernel<float, 8, 8>, p4, a, 8, lk, st);
-        }
-        rc = d->dtype == VSR_BF16 ? launch_attn_p(attn_bwd_q_p_kernel<bf16_t, 4, 4>, p5, a, 4, lq, st)
-                                  : launch_attn_p(attn_bwd_q_p_kernel<float, 4, 4>, p6, a, 4, lq, st);
-        if (rc != VSR_OK) return rc;
-        return d->dtype == VSR_BF16 ? launch_attn_p(attn_bwd_kv_p_kernel<bf16_t, 4, 4>, p7, a, 4, lk, st)
-                                    : launch_attn_p(attn_bwd_kv_p_kernel<float, 4, 4>, p8, a, 4, lk, st);
-    }
-    rc = VSR_ERR_UNSUPPORTED;
-#define X(NT_)                                                                                                        \
-    if (d->Nk == 16 * NT_) {                                                                                          \
-        static VsrDevOnce o1, o3;                                                                                     \
-        rc = d->dtype == VSR_BF16 ? launch_attn(attn_bwd_q_kernel<bf16_t, NT_>, o1, a, 1, wq, lds1, st) \
-                                  : launch_attn(attn_bwd_q_kernel<float, NT_>, o3, a, 1, wq, lds1, st); \
-    }
-    ATTN_NT_CASES(X)
-#undef X
-    if (rc != VSR_OK) return rc;
-    if (d->dtype == VSR_BF16) return launch_attn(attn_bwd_kv_kernel<bf16_t>, o2, a, cdiv(d->Nk, WQ * wk), wk, lds2, st);
-    return launch_attn(attn_bwd_kv_kernel<float>, o4, a, cdiv(d->Nk, WQ * wk), wk, lds2, st);
+    return d->dtype == VSR_BF16 ? attn_bwd<bf16_t>(d, a, (hipStream_t)stream) : attn_bwd<float>(d, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

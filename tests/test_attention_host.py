@@ -121,7 +121,7 @@ def test_nq_160_is_refused_by_the_backward_only():
 
 def test_window_attention_core_refuses_an_odd_head_dim(monkeypatch):
     from vsrlab_amd import functional as VF
-    monkeypatch.setattr(VF, "_require_gpu", lambda t: None)
+    monkeypatch.setattr(VF.attention, "_require_gpu", lambda t: None)        # where window_attention_core looks it up
     qkv = torch.zeros(2, 64, 3 * 3 * 15)
     with pytest.raises(NotImplementedError):
         VF.window_attention_core(qkv, None, torch.zeros(10, 3), torch.zeros(64, 64, dtype=torch.int64), None, 3, 0.25, "fp32")
@@ -134,7 +134,7 @@ def test_window_attention_core_refuses_an_odd_head_dim(monkeypatch):
 # --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_fp64_restatement_equals_the_oracle(tag):
-    """attention_fp64, descriptor by descriptor as functional.py issues them (self attention into channels [C, 2C) or [0, C), the two
+    """attention_fp64, descriptor by descriptor as functional/attention.py issues them (self attention into channels [C, 2C) or [0, C), the two
     mutual attentions into the two halves of the rows), between the oracle's own qkv and proj Linears: the module output of
     oracle/vrt_attention_oracle.window_attention_forward to 1e-10, and with it the reference's golden output."""
     import torch.nn.functional as F

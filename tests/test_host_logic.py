@@ -485,3 +485,72 @@ def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path, monkeypa
     b, c = dump(tmp_path / "b"), dump(tmp_path / "c")
     assert b["params"].shape == (1000,) and np.isin(b["params"], flat_p.numpy()).all()
     assert all(np.array_equal(b[k], c[k]) for k in b) and np.array_equal(a["sr_sample"], b["sr_sample"])
+
+
+def test_functional_surface_is_the_parents():
+    """vsrlab_amd.functional was one module and is a package by op family: tests/golden/functional_names.txt is the module's
+    attribute surface as recorded before the split (name and kind; without dunders, imported modules and the standard library's
+    typing names; ``_JPEG_DT`` under the name it was given then, ``_STORAGE_DT``).  Every name still resolves on the package with
+    its kind, every function and class is defined in a submodule (``BasicVSRDesc``, which the module re-exported from ``_lib``,
+    is still that class), and no two submodules define one name."""
+    import ast
+    import types
+    from vsrlab_amd import _lib, functional as VF
+
+    def kind(v):
+        if isinstance(v, type):
+            return "class"
+        if isinstance(v, types.FunctionType):
+            return "function"
+        return "int" if isinstance(v, int) and not isinstance(v, bool) else "other"
+
+    with open(os.path.join(ROOT, "tests", "golden", "functional_names.txt")) as f:
+        listed = [line.split() for line in f.read().splitlines() if line]
+    assert len(listed) == 110 and [n for n, _ in listed] == sorted(n for n, _ in listed)
+    for name, want in listed:
+        v = getattr(VF, name)                                # AttributeError: the name is gone
+        assert kind(v) == want, (name, kind(v), want)
+        if name == "BasicVSRDesc":
+            assert v is _lib.BasicVSRDesc
+        elif want in ("function", "class"):
+            assert v.__module__.startswith("vsrlab_amd.functional."), (name, v.__module__)
+    assert not hasattr(VF, "_JPEG_DT")
+    owner = {}
+    pkg = os.path.dirname(VF.__file__)
+    for fname in sorted(os.listdir(pkg)):
+        if not fname.endswith(".py") or fname == "__init__.py":
+            continue
+        with open(os.path.join(pkg, fname)) as f:
+            body = ast.parse(f.read()).body
+        for node in body:
+            if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+                names = [node.name]
+            elif isinstance(node, ast.Assign):
+                names = [t.id for t in node.targets if isinstance(t, ast.Name)]
+            elif isinstance(node, ast.AnnAssign):
+                names = [node.target.id]
+            else:
+                names = []
+            for n in names:
+                assert n not in owner, (n, owner[n], fname)
+                owner[n] = fname
+    assert {n for n, _ in listed} - {"BasicVSRDesc", "DT_BF16", "DT_F32"} == set(owner)
+    # module state has one home: the package reads it there, it holds no copy
+    assert owner["_ARENA_MODE"] == "basicvsr.py" and "_ARENA_MODE" not in vars(VF) and "_chain_timeouts_seen" not in vars(VF)
+    VF.set_arena_mode("diet")
+    try:
+        assert VF._ARENA_MODE == VF.basicvsr._ARENA_MODE == 1 and VF.arena_mode() == 1
+    finally:
+        VF.set_arena_mode(None)
+    assert VF._ARENA_MODE is None
+
+
+def test_the_satellite_loaders_load_once_and_type_every_entry():
+    from vsrlab_amd import _lib
+    for load, table in ((_lib.load_spatial_corr, _lib.SPATIAL_CORR_SIGNATURES), (_lib.load_jpeg, _lib.JPEG_SIGNATURES),
+                        (_lib.load_warp_taps, _lib.WARP_TAPS_SIGNATURES)):
+        lib = load()
+        assert load() is lib and lib is not _lib.load()
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            assert fn.restype is res and fn.argtypes == args, name

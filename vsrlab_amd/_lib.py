@@ -209,85 +209,56 @@ WARP_TAPS_SIGNATURES = {
 }
 WARP_TAPS_EXPORTS = tuple(WARP_TAPS_SIGNATURES)
 
-_lib = None
-_spatial_corr_lib = None
-_jpeg_lib = None
-_warp_taps_lib = None
+# One row per library: its path, the signatures of its ABI, and those of its debug hooks, which only a library that VSRLAB_AMD_LIB
+# names (another build of libvsrlab_hip.so, e.g. a parent commit's for an A/B run) may predate.  _loaded: one slot per library.
+_LIBS = {
+    "hip": (LIB_PATH, _SIGNATURES, DEBUG_SIGNATURES),
+    "spatial_corr": (SPATIAL_CORR_LIB_PATH, SPATIAL_CORR_SIGNATURES, {}),
+    "jpeg": (JPEG_LIB_PATH, JPEG_SIGNATURES, {}),
+    "warp_taps": (WARP_TAPS_LIB_PATH, WARP_TAPS_SIGNATURES, {}),
+}
+_loaded = {}
 
 
-def load_warp_taps():
-    """Load libvsrlab_warp_taps.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
-    global _warp_taps_lib
-    if _warp_taps_lib is None:
-        if not os.path.exists(WARP_TAPS_LIB_PATH):
+def _load(key):
+    """Load a library (once) and set the types of its entries.  Raises RuntimeError if it has not been built: a missing kernel is an
+    error."""
+    if key not in _loaded:
+        path, signatures, hooks = _LIBS[key]
+        if not os.path.exists(path):
             raise RuntimeError(
-                f"vsrlab_amd: HIP library not built ({WARP_TAPS_LIB_PATH} missing). Run "
+                f"vsrlab_amd: HIP library not built ({path} missing). Run "
                 "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
-        lib = ctypes.CDLL(WARP_TAPS_LIB_PATH)
-        for name, (res, args) in WARP_TAPS_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _warp_taps_lib = lib
-    return _warp_taps_lib
-
-
-def load_jpeg():
-    """Load libvsrlab_jpeg.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
-    global _jpeg_lib
-    if _jpeg_lib is None:
-        if not os.path.exists(JPEG_LIB_PATH):
-            raise RuntimeError(
-                f"vsrlab_amd: HIP library not built ({JPEG_LIB_PATH} missing). Run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
-        lib = ctypes.CDLL(JPEG_LIB_PATH)
-        for name, (res, args) in JPEG_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _jpeg_lib = lib
-    return _jpeg_lib
-
-
-def load_spatial_corr():
-    """Load libvsrlab_spatial_corr.so (once).  Raises RuntimeError if it has not been built: a missing kernel is an error."""
-    global _spatial_corr_lib
-    if _spatial_corr_lib is None:
-        if not os.path.exists(SPATIAL_CORR_LIB_PATH):
-            raise RuntimeError(
-                f"vsrlab_amd: HIP library not built ({SPATIAL_CORR_LIB_PATH} missing). Run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
-        lib = ctypes.CDLL(SPATIAL_CORR_LIB_PATH)
-        for name, (res, args) in SPATIAL_CORR_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _spatial_corr_lib = lib
-    return _spatial_corr_lib
-
-
-def load():
-    """Load libvsrlab_hip.so (once).  Raises RuntimeError if it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"vsrlab_amd: HIP library not built ({LIB_PATH} missing). Run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C vsrlab_amd/csrc`.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in DEBUG_SIGNATURES.items():
-            # the project's own build must have them (AttributeError, as for the ABI above); only a library named by
-            # VSRLAB_AMD_LIB, e.g. a parent commit's for an A/B run, may predate them
-            fn = getattr(lib, name, None) if os.environ.get("VSRLAB_AMD_LIB") else getattr(lib, name)
+        lib = ctypes.CDLL(path)
+        may_lack = hooks if os.environ.get("VSRLAB_AMD_LIB") else {}
+        for name, (res, args) in {**signatures, **hooks}.items():
+            # AttributeError if the ABI lost a symbol, or the project's own build a hook
+            fn = getattr(lib, name, None) if name in may_lack else getattr(lib, name)
             if fn is not None:
                 fn.restype = res
                 fn.argtypes = args
-        _lib = lib
-    return _lib
+        _loaded[key] = lib
+    return _loaded[key]
+
+
+def load():
+    """libvsrlab_hip.so."""
+    return _load("hip")
+
+
+def load_spatial_corr():
+    """libvsrlab_spatial_corr.so."""
+    return _load("spatial_corr")
+
+
+def load_jpeg():
+    """libvsrlab_jpeg.so."""
+    return _load("jpeg")
+
+
+def load_warp_taps():
+    """libvsrlab_warp_taps.so."""
+    return _load("warp_taps")
 
 
 def check(status, what):

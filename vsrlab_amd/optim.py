@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from .functional import _ptr, _stream
 
-_ALIGN = 64          # floats: 256-byte slots, like the gradient arena of functional.py
+_ALIGN = 64          # floats: 256-byte slots, like the gradient arena of functional/basicvsr.py
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -173,21 +173,36 @@ def test_unet_discriminator_vs_golden(dtype):
 
 def test_discriminator_bf16_many_tiles_per_workgroup():
     """conv_wide2 is persistent: at config 3 a workgroup walks ~125 tiles, at the golden's 32x48 frames exactly one.  Here the
-    workgroups per output column are capped at 3 (VSRLAB_AMD_WIDE2_MAX_WG, a test knob), so on a (1,3,72,136) frame every wide layer
-    runs several tiles per workgroup (ragged ones included): tile-to-tile DMA ring, epilogue drain, K-split reduction.  bf16 vs the
-    fp64 oracle with the noise-floor criterion."""
+    workgroups per output column are capped at 3 (vsr_debug_wide2_set_max_wg, a test knob that holds from the call on, whatever was
+    launched before it in this process), so on a (1,3,72,136) frame the wide layers at H and H/2 run several tiles per workgroup (ragged
+    ones included): tile-to-tile DMA ring, epilogue drain, K-split reduction.  That the cap is in force is asserted on the launcher's own
+    grid choice (vsr_debug_wide_grid).  bf16 vs the fp64 oracle with the noise-floor criterion."""
     dev = _gpu()
-    import os
+    import ctypes
+    import vsrlab_amd
     from test_hip_parity import _noise_floor_check
-    os.environ["VSRLAB_AMD_WIDE2_MAX_WG"] = "3"
+    lib = vsrlab_amd._lib.load()
+
+    def grid(ncob, out_step, h, w):
+        out = (ctypes.c_int * 3)()
+        assert lib.vsr_debug_wide_grid(ncob, out_step, 1, h, w, 0, 0, out) == 0
+        return tuple(out)
+
+    assert lib.vsr_debug_wide2_set_max_wg(3) == 0
     try:
+        # conv_4 (512 -> 256 at H/4 = 18 x 34: two columns of 128 output channels, 6 tiles) gets 3 workgroups per column, not 6;
+        # conv_6 (128 -> 64 at 72 x 136, K-split) walks its 45 tiles on 3 workgroups, conv_1's data gradient likewise per phase
+        assert grid(4, 1, 18, 34) == (3, 2, 6)
+        assert grid(1, 1, 72, 136) == (3, 1, 45) and grid(1, 2, 36, 68) == (3, 4, 15)
         d = _make_d(dev, "bf16")
         img = rand(21, 1, 3, 72, 136).to(dev).requires_grad_(True)
         cot = rand(22, 1, 1, 72, 136, lo=-1, hi=1).to(dev)
         out = d(img)
         torch.mean(out * cot).backward()
+        torch.cuda.synchronize()
     finally:
-        del os.environ["VSRLAB_AMD_WIDE2_MAX_WG"]
+        assert lib.vsr_debug_wide2_set_max_wg(0) == 0
+    assert grid(4, 1, 18, 34)[0] == 6
     sd = {k: v.double() for k, v in O.keyed_state_dict(D.disc_param_shapes(3, 64)).items()}
     leaves = {k: v.clone().requires_grad_(not k.endswith(("weight_u", "weight_v"))) for k, v in sd.items()}
     img64 = rand(21, 1, 3, 72, 136).double().requires_grad_(True)

@@ -209,8 +209,9 @@ def _exported_vsr_symbols(path):
 def test_the_hooks_are_additions_to_an_unchanged_abi():
     """The library's exported `vsr_` symbols, enumerated from its dynamic symbol table: before the hooks it exported 74 -- the 67 of
     include/vsrlab_hip.h (= EXPORTS) and 7 vsr_debug_* entries (OTHER_DEBUG_EXPORTS) -- and now exactly those plus the 7
-    reconstruction-tail hooks (81), the 7 propagation-trunk hooks (88) and the 7 SPyNet hooks (95), by name: nothing else, nothing missing.
-    The ABI number stays."""
+    reconstruction-tail hooks (81), the 7 propagation-trunk hooks (88), the 7 SPyNet hooks (95) and the 10 entries of the GAN side's pin
+    (105: seven launch hooks, the discriminator's plan, the grid of a conv_wide2 launch and the setter of its test cap), by name: nothing
+    else, nothing missing.  The ABI number stays."""
     L, lib = _lib()
     import os
     import re
@@ -220,12 +221,15 @@ def test_the_hooks_are_additions_to_an_unchanged_abi():
     tail = {"vsr_debug_tail_" + k for k in ("last2_fwd", "last2_dgrad", "planar_c64", "last2_wgrad", "conv_unshuffle", "ps_dgrad", "ps_wgrads")}
     trunk = {"vsr_debug_trunk_" + k for k in ("conv", "stem", "stem_dgrad", "point", "wgrad_cc", "stem_wgrads", "chain")}
     spy = {"vsr_debug_spy_" + k for k in ("conv", "dgrad", "wgrad", "prepare", "prepare_bwd", "dres", "planar")}
-    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk | spy and len(tail | trunk | spy) == 21
+    wide = {"vsr_debug_wide_" + k for k in ("conv", "wgrad", "up2_fwd", "up2_bwd", "mask", "grid")} | {"vsr_debug_vgg_pool", "vsr_debug_vgg_tap",
+                                                                                                         "vsr_debug_disc_plan", "vsr_debug_wide2_set_max_wg"}
+    assert len(wide) == 10
+    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk | spy | wide and len(tail | trunk | spy | wide) == 31
     assert not set(L.DEBUG_SIGNATURES) & declared and not set(L.DEBUG_SIGNATURES) & set(L.OTHER_DEBUG_EXPORTS)
     got = _exported_vsr_symbols(L.LIB_PATH)
     before = set(L.EXPORTS) | set(L.OTHER_DEBUG_EXPORTS)
     assert got - set(L.DEBUG_SIGNATURES) == before, (sorted(got - set(L.DEBUG_SIGNATURES) - before), sorted(before - got))
-    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7 + 7
+    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7 + 7 + 10
     for name in L.DEBUG_SIGNATURES:
         assert getattr(lib, name).argtypes == L.DEBUG_SIGNATURES[name][1]
 

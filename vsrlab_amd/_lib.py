@@ -179,6 +179,18 @@ DEBUG_SIGNATURES = {
     "vsr_debug_spy_prepare_bwd": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "vsr_debug_spy_dres": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
     "vsr_debug_spy_planar": (c_int, [c_int, _P, _P, _P, _P, _P, _LL, c_int, c_int, c_int, c_int, _P]),
+    # csrc/wide_hooks.hip (dtype first; vsr_debug_wide_conv: mode, cout, cin next, wpack_elems and slab_floats are long long), the plan
+    # hook of csrc/disc_engine.hip and the two host-only grid entries (csrc/conv_wide.hip's cap setter; the grid of a conv_wide2 launch)
+    "vsr_debug_wide_conv": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _LL, _P, c_int, c_float, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_wide_wgrad": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _LL, c_int, c_int, c_int, _P]),
+    "vsr_debug_wide_up2_fwd": (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_wide_up2_bwd": (c_int, [c_int, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_wide_mask": (c_int, [c_int, _P, _P, _P, c_float, _LL, _P]),
+    "vsr_debug_vgg_pool": (c_int, [c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_vgg_tap": (c_int, [c_int, _P, _P, c_int, c_float, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_disc_plan": (c_int, [ctypes.POINTER(DiscDesc), c_int, _P, c_int]),
+    "vsr_debug_wide_grid": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_wide2_set_max_wg": (c_int, [c_int]),
 }
 
 # libvsrlab_spatial_corr.so (include/vsrlab_spatial_corr.h): the local correlation, a library of its own -- the symbols that

@@ -197,7 +197,6 @@ static inline int vsr_num_cus() {
 #include <cstdlib>
 struct VsrEnvSwitches {
     bool generic_conv, generic_wgrad, single_stream;
-    int wide2_max_wg;
 };
 static inline const VsrEnvSwitches& vsr_env() {
     static const VsrEnvSwitches s = [] {
@@ -206,8 +205,6 @@ static inline const VsrEnvSwitches& vsr_env() {
         v.generic_conv = on("VSRLAB_AMD_GENERIC_CONV");
         v.generic_wgrad = on("VSRLAB_AMD_GENERIC_WGRAD");
         v.single_stream = on("VSRLAB_AMD_SINGLE_STREAM");
-        const char* e = getenv("VSRLAB_AMD_WIDE2_MAX_WG");
-        v.wide2_max_wg = e ? atoi(e) : 0;
         return v;
     }();
     return s;

@@ -27,6 +27,12 @@ namespace {
 constexpr int TW = 32, RW = 2, TH = 8, NTHREADS = 256;
 constexpr int TWH = TW + 2, THH = TH + 2, NPIX = THH * TWH;
 
+// The activation-gradient mask is v * (m > 0 ? 1 : slope).  With a ReLU mask (slope 0) that product is -0 for a negative v, and the rule
+// is that what a ReLU mask zeroes is +0: the kernels add mask_zero_fix(slope) to the product, +0 for slope 0 ((-0) + (+0) = +0, every other
+// value keeps its bits) and -0 otherwise (x + (-0) = x for every x: a LeakyReLU mask keeps every bit).  One add with a launch-uniform
+// operand: no branch, no select, no register
+__device__ __forceinline__ float mask_zero_fix(float slope) { return slope == 0.f ? 0.f : -0.f; }
+
 __device__ __forceinline__ int wswz(int p, int c) { return c ^ ((p >> 1) & 7); }     // 8 chunks per 64-channel row
 
 struct WideArgs {
@@ -204,8 +210,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_wide_kernel(const WideArgs a) {
                 }
                 if (a.aux) {
                     const Vec4<T> m = *reinterpret_cast<const Vec4<T>*>(reinterpret_cast<const T*>(a.aux) + o);
+                    const float mz = mask_zero_fix(a.slope);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] *= (to_f(m.v[j]) > 0.f ? 1.f : a.slope);
+                    for (int j = 0; j < 4; ++j) v[j] = v[j] * (to_f(m.v[j]) > 0.f ? 1.f : a.slope) + mz;
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) t.v[j] = (T)v[j];
@@ -564,8 +571,9 @@ __global__ __launch_bounds__(W2_NT, 1) void conv_wide2_kernel(const Wide2Args a)
                             for (int j = 0; j < 4; ++j) v[j] += (float)rr[mb][nb].v[j];
                         }
                         if (a.aux) {
+                            const float mz = mask_zero_fix(a.slope);
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] *= ((float)mm[mb][nb].v[j] > 0.f ? 1.f : a.slope);
+                            for (int j = 0; j < 4; ++j) v[j] = v[j] * ((float)mm[mb][nb].v[j] > 0.f ? 1.f : a.slope) + mz;
                         }
                         w2bf4 out;
 #pragma unroll
@@ -727,8 +735,9 @@ __global__ void up2_bwd_kernel(const T* __restrict__ dout, T* __restrict__ din, 
         if (dmask) {
             float mv[8];
             ld8<T>(m + o, mv);
+            const float mz = mask_zero_fix(slope);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] *= (mv[j] > 0.f ? 1.f : slope);
+            for (int j = 0; j < 8; ++j) acc[j] = acc[j] * (mv[j] > 0.f ? 1.f : slope) + mz;
             st8<T>(dmask + o, acc);
         }
     }
@@ -752,8 +761,9 @@ __global__ void mask_pm_kernel(const T* __restrict__ g, const T* __restrict__ m,
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
         float f[8], mv[8];
         ld8<T>(g + i * 8, f); ld8<T>(m + i * 8, mv);
+        const float mz = mask_zero_fix(slope);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] *= (mv[j] > 0.f ? 1.f : slope);
+        for (int j = 0; j < 8; ++j) f[j] = f[j] * (mv[j] > 0.f ? 1.f : slope) + mz;
         st8<T>(out + i * 8, f);
     }
 }
@@ -906,6 +916,22 @@ __global__ void bce_logits_kernel(const float* __restrict__ x, float* __restrict
 }  // namespace
 
 // ======================================= host side (C++ linkage, used by disc_engine.hip) ==================================
+// test knob: a process-wide cap on conv_wide2's workgroups per output column, so that small frames exercise the many-tiles-per-workgroup
+// path (vsr_debug_wide2_set_max_wg; 0 = none).  A launch that names its own cap (VsrWideConv::max_wg) does not read it.
+static int g_wide2_max_wg = 0;
+
+void vsr_wide2_grid(int ncob, int out_step, int N, int H, int W, int max_wg, int num_cus, int* nwx_out, int* cols_out, int* tiles_out) {
+    const bool ks = (ncob & 1) != 0;
+    const int cols = (ks ? ncob : ncob / 2) * (out_step == 2 ? 4 : 1);
+    const int tiles = N * cdiv(H, TH) * cdiv(W, TW);
+    int nwx = num_cus / cols;
+    if (nwx < 1) nwx = 1;
+    if (nwx > tiles) nwx = tiles;
+    const int cap = max_wg > 0 ? max_wg : __atomic_load_n(&g_wide2_max_wg, __ATOMIC_RELAXED);
+    if (cap > 0 && nwx > cap) nwx = cap;
+    *nwx_out = nwx; *cols_out = cols; *tiles_out = tiles;
+}
+
 int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t st) {
     if (!c.x || !c.y || (!c.wpack && !c.wpack2) || c.N < 1 || c.H < 1 || c.W < 1 || c.nsl < 1 || c.ncob < 1) return VSR_ERR_BADARG;
     if ((c.xC & 63) || (c.yC & 63) || c.nsl * 64 > c.xC || c.ncob * 64 > c.yC) return VSR_ERR_BADARG;
@@ -938,15 +964,8 @@ int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t st) {
         for (int i = 0; i < 4; ++i) b.tapmask[i] = a.tapmask[i];
         b.bias = c.bias; b.y = c.y; b.y_nstride = a.y_nstride; b.yCP = c.yC >> 3; b.Hy = c.Hy; b.Wy = c.Wy; b.out_step = c.out_step;
         b.ncp = ks ? c.ncob : c.ncob / 2; b.act = c.act; b.slope = c.slope; b.res = c.res; b.aux = c.aux; b.y_act = c.y_act;
-        const int cols = b.ncp * nph;
-        const int tiles = c.N * cdiv(c.H, TH) * cdiv(c.W, TW);
-        int nwx = vsr_num_cus() / cols;
-        if (nwx < 1) nwx = 1;
-        if (nwx > tiles) nwx = tiles;
-        {   // test knob: cap the workgroups per column so that small frames exercise the many-tiles-per-workgroup path
-            const int cap = vsr_env().wide2_max_wg;
-            if (cap > 0 && nwx > cap) nwx = cap;
-        }
+        int nwx, cols, tiles;
+        vsr_wide2_grid(c.ncob, c.out_step, c.N, c.H, c.W, c.max_wg, vsr_num_cus(), &nwx, &cols, &tiles);
         static VsrDevOnce once2, once2k;
         if (ks) {
             { const int rc = vsr_set_max_dynamic_lds(once2k, reinterpret_cast<const void*>(conv_wide2_kernel<true>), W2_LDS); if (rc != VSR_OK) return rc; }
@@ -1060,6 +1079,13 @@ int vsr_launch_mask_pm(int dtype, const void* g, const void* m, void* out, float
 }
 
 extern "C" {
+
+// (test knob, not in the header) cap conv_wide2's workgroups per output column for every later launch of this process; 0 lifts it
+int vsr_debug_wide2_set_max_wg(int max_wg) {
+    if (max_wg < 0) return VSR_ERR_BADARG;
+    __atomic_store_n(&g_wide2_max_wg, max_wg, __ATOMIC_RELAXED);
+    return VSR_OK;
+}
 
 int vsr_spectral_norm(const float* w_orig, float* u, float* v, float* w_out, float* sigma, int rows, int cols, int training, void* stream) {
     if (!w_orig || !u || !v || !w_out || !sigma || rows < 1 || rows > 512 || cols < 1) return VSR_ERR_BADARG;

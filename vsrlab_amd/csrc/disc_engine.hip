@@ -17,7 +17,7 @@
 // The pre-residual activations a4, a5, a6 are kept besides the sums: LeakyReLU' needs the sign of the activation, which
 // the sum with the skip no longer has.
 #include <vector>
-#include "host.h"
+#include "wide_recipes.h"
 
 namespace {
 
@@ -60,6 +60,7 @@ struct DPlan {
         u3 = b.take(pm(h / 4, w / 4, 512)); a4 = b.take(pm(h / 4, w / 4, 256)); u4 = b.take(pm(h / 2, w / 2, 256));
         a5 = b.take(pm(h / 2, w / 2, 128)); u5 = b.take(pm(h, w, 128)); a6 = b.take(pm(h, w, 64)); s6 = b.take(pm(h, w, 64));
         o7 = b.take(pm(h, w, 64)); o8 = b.take(pm(h, w, 64));
+        slab = 0;
         if (need_backward) {
             // backward scratch for ONE frame: the backward walks the batch frame by frame (weight gradients accumulate), so a
             // 7-frame 2160x3840 batch keeps 76 GB of activations but only 8.5 GB of scratch (not 60)
@@ -69,7 +70,7 @@ struct DPlan {
             du3 = b.take(pm1(h / 4, w / 4, 512)); dc3 = b.take(pm1(h / 8, w / 8, 512)); dc2 = b.take(pm1(h / 4, w / 4, 256));
             dc1 = b.take(pm1(h / 2, w / 2, 128)); dc0 = b.take(pm1(h, w, 64));
             // partials of 3x3 64 -> 64 blocks: one per workgroup (wgrad_slab_bytes()) or per pair and pixel part of a pair-batched launch
-            slab = b.take((size_t)(VSR_WGRAD_NWG > VSR_WGRAD_MAX_PAIR_SLABS ? VSR_WGRAD_NWG : VSR_WGRAD_MAX_PAIR_SLABS) * wgrad_slab_stride3() * 4);
+            slab = b.take(wide_slab_floats() * 4);
         }
         total = b.off;
         return VSR_OK;
@@ -104,50 +105,18 @@ struct DCtx {
         a.src[0] = x; a.wpack = at(wpack); a.dst[0] = y; a.act = act; a.aux[0] = aux; a.mask_mode = mask;
         return vsr_launch_conv(dtype, 3, 1, 64, 64, 0, 64, EPI_NHWC, a, st);
     }
+    // the wide launches: the shared recipes (wide_recipes.h) on this plan's batch, slope and slab
+    WideCtx wc() const { return WideCtx{st, dtype, p.n, (float*)at(p.slab)}; }
     int wide(const void* x, int xC, int Hx, int Wx, int in_step, int H, int W, size_t wpack, bool w2, void* y, int yC, int out_step, int act,
              void* y_act = nullptr, const void* res = nullptr, void* y_pre = nullptr, const void* aux = nullptr) const {
-        VsrWideConv c = {};
-        c.x = x; c.xC = xC; c.Hx = Hx; c.Wx = Wx; c.in_step = in_step; c.nsl = xC / 64;
-        c.N = p.n; c.H = H; c.W = W; c.bias = nullptr;
-        if (w2) c.wpack2 = at(wpack); else c.wpack = at(wpack);
-        c.y = y; c.yC = yC; c.Hy = H * out_step; c.Wy = W * out_step; c.out_step = out_step; c.ncob = yC / 64;
-        c.act = act; c.slope = SLOPE; c.y_act = y_act; c.res = res; c.y_pre = y_pre; c.aux = aux;
-        return vsr_launch_conv_wide(dtype, c, st);
+        return wc().wide(x, xC, Hx, Wx, in_step, H, W, at(wpack), w2, nullptr, y, yC, out_step, act, SLOPE, y_act, res, y_pre, aux);
     }
-    // one 64 x 64 block of a weight gradient: slabs -> reduce.  view < 0: 3x3 layer (OIHW with 9 taps); else parity view of a 4x4 layer
     int wgrad_block(const void* x, int xC, int x_slice, int Hx, int Wx, int x_step, int view, const void* dy, int dyC, int dy_slice,
                     int H, int W, float* gw, int cin_total, int co0, int ci0) const {
-        WgradArgs a = {};
-        a.N = p.n; a.H = H; a.W = W; a.nseg = 1;
-        a.x[0] = x; a.x_step = x_step; a.x_oy = view >= 0 ? (view >> 1) : 0; a.x_ox = view >= 0 ? (view & 1) : 0;
-        a.Hx = Hx; a.Wx = Wx; a.x_nstride = pm_image_elems(Hx, Wx, xC); a.x_ctotal = xC; a.x_coff = x_slice * 8;
-        a.dy[0] = dy; a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, dyC); a.dy_ctotal = dyC; a.dy_coff = dy_slice * 8;
-        const WgradShape shape = {3, 64, false, 64, false};
-        if (view < 0) return wgrad_run(st, dtype, (float*)at(p.slab), a, shape, {64, 64, gw + (size_t)co0 * cin_total * 9, cin_total, ci0, 1, 0, nullptr, 1});
-        int nslabs = 0;
-        CK(wgrad_launch(st, dtype, (float*)at(p.slab), a, shape, true, &nslabs));
-        return vsr_launch_wgrad_reduce_s2((const float*)at(p.slab), nslabs, a.slab_stride, gw, cin_total, co0, ci0, view, st);
+        return wc().wgrad_block(x, xC, x_slice, Hx, Wx, x_step, view, dy, dyC, dy_slice, H, W, gw, cin_total, co0, ci0);
     }
-    // the whole weight gradient of a wide layer: x (xC channels; views == 4: the four parity views of a 4x4 stride-2 conv's input),
-    // dy (dyC channels).  bf16: every (view, cout block, cin slice) pair in one launch + one reduction; fp32: pair by pair.
     int wgrad_layer(const void* x, int xC, int Hx, int Wx, int views, const void* dy, int dyC, int H, int W, float* gw) const {
-        const int nsl = xC / 64, ncob = dyC / 64, npairs = nsl * ncob * views, x_step = views == 4 ? 2 : 1;
-        if (dtype == VSR_BF16 && npairs > 1) {
-            WgradArgs a = {};
-            a.N = p.n; a.H = H; a.W = W; a.nseg = 1;
-            a.x[0] = x; a.x_step = x_step; a.Hx = Hx; a.Wx = Wx; a.x_nstride = pm_image_elems(Hx, Wx, xC); a.x_ctotal = xC;
-            a.dy[0] = dy; a.dy_step = 1; a.Hy = H; a.Wy = W; a.dy_nstride = pm_image_elems(H, W, dyC); a.dy_ctotal = dyC;
-            a.slab = (float*)at(p.slab); a.slab_stride = wgrad_slab_stride3();
-            const int tiles = p.n * cdiv(H, 8) * cdiv(W, 32);
-            int ksplit = ((512 / npairs) + 7) & ~7;                       // ~512 workgroups per launch
-            if (ksplit < 8) ksplit = 8;
-            const int cap = (tiles + 7) & ~7;
-            if (ksplit > cap) ksplit = cap;
-            return vsr_launch_wgrad_pairs(dtype, a, nsl, ncob, views, ksplit, gw, xC, st);
-        }
-        for (int v = 0; v < views; ++v) for (int o = 0; o < ncob; ++o) for (int s = 0; s < nsl; ++s)
-            CK(wgrad_block(x, xC, s, Hx, Wx, x_step, views == 4 ? v : -1, dy, dyC, o, H, W, gw, xC, 64 * o, 64 * s));
-        return VSR_OK;
+        return wc().wgrad_layer(x, xC, Hx, Wx, views, dy, dyC, H, W, gw);
     }
 };
 
@@ -288,6 +257,22 @@ int disc_backward(const DCtx& c, float* const* g, const float* img, const float*
 }  // namespace
 
 extern "C" {
+
+// (test hook, not in the header; host only) the plan of `d`: offsets[0..12] the activations f0 f1 f2 f3 u3 a4 u4 a5 u5 a6 s6 o7 o8 (byte
+// offsets into the workspace, frame 0), offsets[13..28] the backward scratch d_o8 d_o7 G6 dc6 du5 ds5 dc5 du4 ds4 dc4 du3 dc3 dc2 dc1 dc0
+// slab (need_backward; else -1), offsets[29] the workspace size.  count: entries of `offsets`, VSR_DISC_PLAN_OFFSETS
+#define VSR_DISC_PLAN_OFFSETS 30
+int vsr_debug_disc_plan(const VsrDiscDesc* d, int need_backward, long long* offsets, int count) {
+    if (!d || !offsets || count != VSR_DISC_PLAN_OFFSETS || (need_backward & ~1)) return VSR_ERR_BADARG;
+    DPlan p;
+    CK(p.build(*d, need_backward));
+    const size_t act[13] = {p.f0, p.f1, p.f2, p.f3, p.u3, p.a4, p.u4, p.a5, p.u5, p.a6, p.s6, p.o7, p.o8};
+    const size_t bwd[16] = {p.d_o8, p.d_o7, p.G6, p.dc6, p.du5, p.ds5, p.dc5, p.du4, p.ds4, p.dc4, p.du3, p.dc3, p.dc2, p.dc1, p.dc0, p.slab};
+    for (int i = 0; i < 13; ++i) offsets[i] = (long long)act[i];
+    for (int i = 0; i < 16; ++i) offsets[13 + i] = need_backward ? (long long)bwd[i] : -1;
+    offsets[29] = (long long)p.total;
+    return VSR_OK;
+}
 
 size_t vsr_disc_workspace_bytes(const VsrDiscDesc* d, int need_backward) {
     if (!d) return 0;

@@ -84,8 +84,12 @@ struct VsrWideConv {
     int act; float slope;
     void* y_act; const void* res; void* y_pre; const void* aux;
     const void* wpack2;            // bf16, yC a multiple of 128: weights in conv_wide2's image (vsr_launch_pack_wide2); wpack unused
+    int max_wg;                    // wpack2: at most so many workgroups per output column (0: none, or what vsr_debug_wide2_set_max_wg set)
 };
 int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t st);
+// the grid of conv_wide2 for a launch with `ncob` 64-channel output blocks: *cols output columns (phases x 128-channel blocks, or
+// 64-channel blocks of the K-split form) of *nwx workgroups each over *tiles 8 x 32 tiles.  Host only.  max_wg as VsrWideConv's
+void vsr_wide2_grid(int ncob, int out_step, int N, int H, int W, int max_wg, int num_cus, int* nwx, int* cols, int* tiles);
 long long vsr_wide_pack_elems(int cout, int cin, int mode);
 long long vsr_wide2_pack_elems(int cout, int cin, int mode);
 int vsr_launch_pack_wide2(const float* w, void* dst, int cout, int cin, int mode, hipStream_t st);
@@ -96,6 +100,13 @@ int vsr_launch_up2_bwd(int dtype, const void* dout, void* din, void* dmask, cons
 int vsr_launch_mask_pm(int dtype, const void* g, const void* m, void* out, float slope, long long elems, hipStream_t st);
 int vsr_launch_add_pm(int dtype, const void* a, const void* b, void* out, long long elems, hipStream_t st);
 
-#define VSR_WGRAD_MAX_PAIR_SLABS 1024   // pair-batched wgrad launches: (view, cout block, cin slice) pairs x pixel parts
+// ---- VGG19's own kernels (perceptual_engine.hip), on blocked pixel-major (N, Hi, Wi, C) ----
+int vsr_launch_maxpool2_fwd(int dtype, const void* in, void* out, int N, int Hi, int Wi, int C, hipStream_t st);
+int vsr_launch_maxpool2_bwd(int dtype, const void* a, const void* dp, void* g, int N, int Hi, int Wi, int C, hipStream_t st);
+int vsr_launch_tap_l1(int dtype, const void* s, const void* h, void* g, float scale, int N, int H, int W, int C, double* partial, int nblocks,
+                      hipStream_t st);
+int vsr_launch_tap_sum(const double* partial, double* sums, int N, const int* nblocks5, hipStream_t st);
+
+#define VSR_WGRAD_MAX_PAIR_SLABS 1024  // pair-batched wgrad launches: (view, cout block, cin slice) pairs x pixel parts
 int vsr_launch_wgrad_pairs(int dtype, const WgradArgs& a, int nsl, int ncob, int views, int ksplit, float* gw, int cin_total, hipStream_t st);
 #define VSR_WGRAD_NWG 512   // persistent wgrad workgroups: 2 per CU x 256 CUs

@@ -18,13 +18,13 @@
 // buffer of an activation that is no longer needed, so the backward needs no scratch of its own.
 #include <vector>
 #include "elt.h"
-#include "host.h"
+#include "wide_recipes.h"
 
 namespace {
 
 constexpr int NCONV = 16;
-constexpr int NTAP = 5;
-constexpr int PMAX = 512;                 // block partials per (image, tap)
+constexpr int NTAP = VSR_TAP_N;
+constexpr int PMAX = VSR_TAP_PMAX;        // block partials per (image, tap)
 // features index, output channels, input channels, level (0 = full resolution) of the 16 convolutions of features[:35]
 constexpr int L_IDX[NCONV] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28, 30, 32, 34};
 constexpr int L_CO[NCONV] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512, 512, 512, 512};
@@ -120,7 +120,7 @@ __global__ void maxpool2_bwd_kernel(const T* __restrict__ a, const T* __restrict
 // the image's real pixels (fp32 within an 8-channel chunk, fp64 across chunks and lanes) into partial[n * PMAX + b]; g (may alias
 // h: every element is read before it is written by the same thread) = scale * sign(s - h), sign(0) = 0.  The grid depends on the
 // image geometry only, so an image's sum has the same bits whatever the batch it is computed in.
-constexpr int TAP_NT = 256;
+constexpr int TAP_NT = VSR_TAP_NT;
 template <typename T>
 __global__ __launch_bounds__(TAP_NT) void tap_l1_kernel(const T* __restrict__ s, const T* h, T* g, float scale, int H, int W, int C,
                                                         double* __restrict__ partial) {
@@ -212,12 +212,10 @@ struct PPlan {
         total = b.off;
         return VSR_OK;
     }
-    // blocks of the tap kernel per image: a pure function of the level geometry (>= 8 chunks per thread, <= PMAX)
+    // blocks of the tap kernel per image: a pure function of the level geometry (vsr_tap_blocks)
     int tap_blocks(int t) const {
-        const int lv = L_LV[TAP_CONV[t]], C = L_CO[TAP_CONV[t]];
-        const long long chunks = (long long)Hl[lv] * pm_ws(Wl[lv]) * (C / 8) * 32;
-        long long nb = (chunks + TAP_NT * 8 - 1) / (TAP_NT * 8);
-        return (int)(nb < 1 ? 1 : (nb > PMAX ? PMAX : nb));
+        const int lv = L_LV[TAP_CONV[t]];
+        return vsr_tap_blocks(Hl[lv], Wl[lv], L_CO[TAP_CONV[t]]);
     }
 };
 
@@ -233,45 +231,19 @@ struct PCtx {
         a.src_nstride[0] = pm_image_elems(H, W, 64);
         return a;
     }
+    // the wide and VGG launches: the shared recipes (wide_recipes.h) on this plan's batch
+    WideCtx wc() const { return WideCtx{st, dtype, p.n, nullptr}; }
     // 3x3 stride-1 conv at >= 64 channels on conv_wide (fp32) / conv_wide2 (bf16).  aux: ReLU mask source (slope 0)
     int wide(int k, bool dgrad, const void* x, void* y, int act, const void* aux) const {
         const int lv = L_LV[k], xC = dgrad ? L_CO[k] : L_CI[k], yC = dgrad ? L_CI[k] : L_CO[k];
-        VsrWideConv c = {};
-        c.x = x; c.xC = xC; c.Hx = p.Hl[lv]; c.Wx = p.Wl[lv]; c.in_step = 1; c.nsl = xC / 64;
-        c.N = p.n; c.H = p.Hl[lv]; c.W = p.Wl[lv]; c.bias = dgrad ? nullptr : fat(p.bias[k]);
-        if (dtype == VSR_BF16) c.wpack2 = at(dgrad ? p.wd[k] : p.wf[k]); else c.wpack = at(dgrad ? p.wd[k] : p.wf[k]);
-        c.y = y; c.yC = yC; c.Hy = p.Hl[lv]; c.Wy = p.Wl[lv]; c.out_step = 1; c.ncob = yC / 64;
-        c.act = act; c.slope = 0.f; c.aux = aux;
-        return vsr_launch_conv_wide(dtype, c, st);
+        return wc().wide(x, xC, p.Hl[lv], p.Wl[lv], 1, p.Hl[lv], p.Wl[lv], at(dgrad ? p.wd[k] : p.wf[k]), dtype == VSR_BF16, dgrad ? nullptr : fat(p.bias[k]),
+                         y, yC, 1, act, 0.f, nullptr, nullptr, nullptr, aux);
     }
-    int pool_fwd(int lv, int C, const void* in, void* out) const {
-        const int Wo = p.Wl[lv + 1];
-        const dim3 grid(cdiv(pm_ws(Wo) * 32 * (C / 8), 256), p.Hl[lv + 1], p.n);
-        if (dtype == VSR_BF16) hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, p.Hl[lv], p.Wl[lv], C);
-        else hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, p.Hl[lv], p.Wl[lv], C);
-        HIP_CHECK_RET(hipGetLastError());
-        return VSR_OK;
-    }
-    int pool_bwd(int lv, int C, const void* a, const void* dp, void* g) const {
-        const int Wb = (p.Wl[lv] + 1) / 2, Hb = (p.Hl[lv] + 1) / 2;
-        const dim3 grid(cdiv(pm_ws(Wb) * 32 * (C / 8), 256), Hb, p.n);
-        if (dtype == VSR_BF16) hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)dp, (bf16_t*)g, p.Hl[lv], p.Wl[lv], C);
-        else hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)a, (const float*)dp, (float*)g, p.Hl[lv], p.Wl[lv], C);
-        HIP_CHECK_RET(hipGetLastError());
-        return VSR_OK;
-    }
+    int pool_fwd(int lv, int C, const void* in, void* out) const { return wc().pool_fwd(in, out, p.Hl[lv], p.Wl[lv], C); }
+    int pool_bwd(int lv, int C, const void* a, const void* dp, void* g) const { return wc().pool_bwd(a, dp, g, p.Hl[lv], p.Wl[lv], C); }
     int tap(int t, const void* s, void* h, bool grad, float scale) const {
         const int lv = L_LV[TAP_CONV[t]], C = L_CO[TAP_CONV[t]];
-        double* part = reinterpret_cast<double*>(at(p.partial)) + (size_t)t * p.n * PMAX;
-        const dim3 grid(p.tap_blocks(t), p.n);
-        if (dtype == VSR_BF16)
-            hipLaunchKernelGGL(tap_l1_kernel<bf16_t>, grid, dim3(TAP_NT), 0, st, (const bf16_t*)s, (const bf16_t*)h, grad ? (bf16_t*)h : nullptr, scale,
-                               p.Hl[lv], p.Wl[lv], C, part);
-        else
-            hipLaunchKernelGGL(tap_l1_kernel<float>, grid, dim3(TAP_NT), 0, st, (const float*)s, (const float*)h, grad ? (float*)h : nullptr, scale,
-                               p.Hl[lv], p.Wl[lv], C, part);
-        HIP_CHECK_RET(hipGetLastError());
-        return VSR_OK;
+        return wc().tap(s, h, grad, scale, p.Hl[lv], p.Wl[lv], C, reinterpret_cast<double*>(at(p.partial)) + (size_t)t * p.n * PMAX);
     }
 };
 
@@ -369,6 +341,44 @@ int perc_backward(const PCtx& c, float* dsr) {
 
 }  // namespace
 
+// ===================== the launchers of the kernels above (C++ linkage: wide_recipes.h, wide_hooks.hip) ==========================
+int vsr_launch_maxpool2_fwd(int dtype, const void* in, void* out, int N, int Hi, int Wi, int C, hipStream_t st) {
+    const int Ho = Hi / 2, Wo = Wi / 2;
+    const dim3 grid(cdiv(pm_ws(Wo) * 32 * (C / 8), 256), Ho, N);
+    if (dtype == VSR_BF16) hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, Hi, Wi, C);
+    else hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, Hi, Wi, C);
+    HIP_CHECK_RET(hipGetLastError());
+    return VSR_OK;
+}
+
+int vsr_launch_maxpool2_bwd(int dtype, const void* a, const void* dp, void* g, int N, int Hi, int Wi, int C, hipStream_t st) {
+    const int Wb = (Wi + 1) / 2, Hb = (Hi + 1) / 2;
+    const dim3 grid(cdiv(pm_ws(Wb) * 32 * (C / 8), 256), Hb, N);
+    if (dtype == VSR_BF16) hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)dp, (bf16_t*)g, Hi, Wi, C);
+    else hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)a, (const float*)dp, (float*)g, Hi, Wi, C);
+    HIP_CHECK_RET(hipGetLastError());
+    return VSR_OK;
+}
+
+int vsr_launch_tap_l1(int dtype, const void* s, const void* h, void* g, float scale, int N, int H, int W, int C, double* partial, int nblocks,
+                      hipStream_t st) {
+    const dim3 grid(nblocks, N);
+    if (dtype == VSR_BF16)
+        hipLaunchKernelGGL(tap_l1_kernel<bf16_t>, grid, dim3(TAP_NT), 0, st, (const bf16_t*)s, (const bf16_t*)h, (bf16_t*)g, scale, H, W, C, partial);
+    else
+        hipLaunchKernelGGL(tap_l1_kernel<float>, grid, dim3(TAP_NT), 0, st, (const float*)s, (const float*)h, (float*)g, scale, H, W, C, partial);
+    HIP_CHECK_RET(hipGetLastError());
+    return VSR_OK;
+}
+
+int vsr_launch_tap_sum(const double* partial, double* sums, int N, const int* nblocks5, hipStream_t st) {
+    TapSumArgs ta;
+    for (int t = 0; t < NTAP; ++t) ta.nb[t] = nblocks5[t];
+    hipLaunchKernelGGL(tap_sum_kernel, dim3(cdiv(N * NTAP, 256)), dim3(256), 0, st, partial, sums, N, ta);
+    HIP_CHECK_RET(hipGetLastError());
+    return VSR_OK;
+}
+
 extern "C" {
 
 size_t vsr_perceptual_workspace_bytes(const VsrPerceptualDesc* d) {
@@ -391,14 +401,13 @@ int vsr_perceptual_loss(const VsrPerceptualDesc* d, const float* const* params, 
     CK(perc_pack(c, params));
     CK(perc_forward(c, hr, true));
     CK(perc_forward(c, sr, false));
-    TapSumArgs ta;
+    int nb[NTAP];
     for (int t = 0; t < NTAP; ++t) {
         const int k = TAP_CONV[t];
         CK(c.tap(t, c.at(p.act[k]), c.at(p.htap[t]), p.need_grad != 0, p.need_grad ? scales[t] : 0.f));
-        ta.nb[t] = p.tap_blocks(t);
+        nb[t] = p.tap_blocks(t);
     }
-    hipLaunchKernelGGL(tap_sum_kernel, dim3(cdiv(p.n * NTAP, 256)), dim3(256), 0, c.st, (const double*)c.at(p.partial), sums, p.n, ta);
-    HIP_CHECK_RET(hipGetLastError());
+    CK(vsr_launch_tap_sum((const double*)c.at(p.partial), sums, p.n, nb, c.st));
     if (p.need_grad) CK(perc_backward(c, dsr));
     return VSR_OK;
 }

@@ -221,6 +221,17 @@ WARP_TAPS_SIGNATURES = {
 }
 WARP_TAPS_EXPORTS = tuple(WARP_TAPS_SIGNATURES)
 
+# libvsrlab_losses.so (include/vsrlab_losses.h): the pair reductions of WL1Loss / rmse_loss and the adjoint of the bilinear resize, likewise
+LOSSES_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_losses.so")
+LOSS_L1 = 0
+LOSS_MSE = 1
+LOSSES_SIGNATURES = {
+    "vsr_pixel_loss_scratch_floats": (c_size_t, []),
+    "vsr_pixel_loss_fwd_bwd": (c_int, [c_int, _P, c_int, _P, c_int, _P, _P, _P, c_longlong, _P]),
+    "vsr_resize_bilinear_bwd": (c_int, [_P, _P, c_longlong, c_int, c_int, c_int, c_int, _P]),
+}
+LOSSES_EXPORTS = tuple(LOSSES_SIGNATURES)
+
 # One row per library: its path, the signatures of its ABI, and those of its debug hooks, which only a library that VSRLAB_AMD_LIB
 # names (another build of libvsrlab_hip.so, e.g. a parent commit's for an A/B run) may predate.  _loaded: one slot per library.
 _LIBS = {
@@ -228,6 +239,7 @@ _LIBS = {
     "spatial_corr": (SPATIAL_CORR_LIB_PATH, SPATIAL_CORR_SIGNATURES, {}),
     "jpeg": (JPEG_LIB_PATH, JPEG_SIGNATURES, {}),
     "warp_taps": (WARP_TAPS_LIB_PATH, WARP_TAPS_SIGNATURES, {}),
+    "losses": (LOSSES_LIB_PATH, LOSSES_SIGNATURES, {}),
 }
 _loaded = {}
 
@@ -271,6 +283,11 @@ def load_jpeg():
 def load_warp_taps():
     """libvsrlab_warp_taps.so."""
     return _load("warp_taps")
+
+
+def load_losses():
+    """libvsrlab_losses.so."""
+    return _load("losses")
 
 
 def check(status, what):

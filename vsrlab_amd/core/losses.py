@@ -1,13 +1,17 @@
 """``CharbonnierLoss`` (vsrlab ``src/core/losses.py:10-18``), fused value+gradient HIP kernel; ``AdversarialLoss``;
 ``PerceptualLoss`` (VGG19, ``src/core/losses.py:29-64``) on the HIP perceptual engine; ``OpticalFlowConsistency`` (RAFT-small,
-``src/core/losses.py:79-98``) on the fused HIP correlation lookup."""
+``src/core/losses.py:79-98``) on the fused HIP correlation lookup; ``WL1Loss`` (``:20-27``) and ``rmse_loss`` (``:76-77``) on the fused pair
+reductions of ``libvsrlab_losses.so``; ``LossPipeline`` (``:100-173``), which combines them by configuration."""
 import os
+from copy import deepcopy
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as VF
+from . import pixel_ops
+from .utils import resize
 from ..optical_flow.models.raft.raft import RAFT
 
 
@@ -18,6 +22,25 @@ class CharbonnierLoss(nn.Module):
 
     def forward(self, x, y):
         return VF.charbonnier_loss(x, y, self.eps)
+
+
+class WL1Loss(nn.L1Loss):
+    """``WL1Loss`` (``src/core/losses.py:20-27``): ``weight * mean |x - y|``, one fused value + gradient HIP pass, differentiable w.r.t.
+    both arguments.  As in the reference, ``*args, **kwargs`` reach ``nn.L1Loss.__init__`` and ``forward`` ignores them:
+    ``WL1Loss(2.0, reduction="sum")`` is twice the MEAN."""
+
+    def __init__(self, weight=1.0, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.weight = weight
+
+    def forward(self, x, y):
+        return pixel_ops.l1_loss(x, y) * self.weight
+
+
+def rmse_loss(yhat, y):
+    """``rmse_loss`` (``src/core/losses.py:76-77``): ``sqrt(mean((yhat - y) ** 2))`` on the fused HIP pass.  No epsilon, as in the
+    reference: equal operands give 0 and a NaN gradient."""
+    return pixel_ops.rmse_loss(yhat, y)
 
 
 class AdversarialLoss(nn.Module):
@@ -126,3 +149,74 @@ class OpticalFlowConsistency(nn.Module):
         with torch.no_grad():
             flow_hr = self.of(hr[:, 1:].reshape(-1, c, h, w), hr[:, :-1].reshape(-1, c, h, w))
         return F.l1_loss(flow_sr, flow_hr) * self.weight
+
+
+class LossPipeline(nn.ModuleDict):
+    """``LossPipeline`` (``src/core/losses.py:100-173``): named losses, evaluated as a list of terms on a dict of tensors.
+
+    ``losses``: name -> ``nn.Module`` (registered in sorted-name order; anything else, or a name already present, is a
+    ``ValueError``).  ``pipeline``: a list of ``{name: {'x': key, 'y': key}}`` terms.  ``forward(args)`` sets ``prefix + name +
+    postfix`` to 0 for every loss and for ``'loss'``, then adds every term, in order, to its loss's key and to the total: a loss that
+    the pipeline names twice accumulates into one key.  The dict that came in is the dict that is returned.
+
+    A key that contains ``match`` is read without its ``match_`` prefix and resized (``core.utils.resize``: bilinear, on the HIP
+    kernel, differentiable) to the (h, w) of the other operand; the ``x`` key is tested first and only one side is matched.
+
+    Deviation: ``clone(prefix, postfix)`` raises ``NameError`` in the reference, which never imports ``deepcopy``.  Here
+    it works: an independent deep copy under the new names."""
+
+    def __init__(self, losses, pipeline, prefix=None, postfix=None):
+        super().__init__()
+        self.prefix = prefix
+        self.postfix = postfix
+        self.pipeline = pipeline
+        self.losses = losses
+        self.add_losses(losses)
+
+    def add_losses(self, losses):
+        for name in sorted(losses.keys()):
+            loss = losses[name]
+            if not isinstance(loss, nn.Module):
+                raise ValueError(f"Value {loss} belonging to key {name} is not an instance of `nn.Module`")
+            if name in self:
+                raise ValueError(f"Encountered two losses both named {name}")
+            self[name] = loss
+
+    def _set_name(self, base):
+        return ("" if self.prefix is None else self.prefix) + base + ("" if self.postfix is None else self.postfix)
+
+    def set_keys(self, args):
+        for name in list(self.losses.keys()) + ["loss"]:
+            args[self._set_name(name)] = 0
+        return args
+
+    def clone(self, prefix=None, postfix=None):
+        other = deepcopy(self)
+        if prefix:
+            other.prefix = prefix
+        if postfix:
+            other.postfix = postfix
+        return other
+
+    @staticmethod
+    def match_shapes(matching, target):
+        return resize(matching, tuple(target.shape[-2:])), target
+
+    def get_loss(self, args, cfg):
+        name, keys = list(cfg.items())[-1]                    # a term with several entries evaluates its last, as the reference's loop does
+        x_key, y_key = keys["x"], keys["y"]
+        if "match" in x_key:
+            x, y = self.match_shapes(args[x_key.removeprefix("match_")], args[y_key])
+        elif "match" in y_key:
+            y, x = self.match_shapes(args[y_key.removeprefix("match_")], args[x_key])
+        else:
+            x, y = args[x_key], args[y_key]
+        return self[name](x, y), name
+
+    def forward(self, args: dict):
+        args = self.set_keys(args)
+        for cfg in self.pipeline:
+            loss, name = self.get_loss(args, cfg)
+            args[self._set_name(name)] += loss
+            args[self._set_name("loss")] += loss
+        return args

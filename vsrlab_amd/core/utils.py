@@ -20,24 +20,40 @@ import torch
 
 from .. import _lib
 from ..functional import _f32c, _ptr, _require_gpu, _stream
+from .pixel_ops import resize_bilinear_backward
+
+
+class _ResizeFn(torch.autograd.Function):
+    """One launch forward (``vsr_resize_bilinear``); the backward is its adjoint (``pixel_ops.resize_bilinear_backward``)."""
+
+    @staticmethod
+    def forward(ctx, x, h, w):
+        H, W = x.shape[-2:]
+        x32 = _f32c(x)
+        out = torch.empty(x.shape[:-2] + (h, w), dtype=torch.float32, device=x.device)
+        planes = x32.numel() // (H * W)
+        lib = _lib.load()
+        _lib.check(lib.vsr_resize_bilinear(_ptr(x32), _ptr(out), planes, H, W, h, w, _stream()), "resize_bilinear")
+        ctx.in_size, ctx.in_dtype = (H, W), x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError("vsrlab_amd: resize has no double backward (create_graph=True is not supported)")
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return resize_bilinear_backward(g, *ctx.in_size).to(ctx.in_dtype), None, None
 
 
 def resize(x: torch.Tensor, size, interpolation: str = "bilinear", align_corners=None, antialias: bool = False) -> torch.Tensor:
     """``kornia.geometry.transform.resize(x, (h, w))`` for (..., H, W) tensors: bilinear, align_corners=False, no
-    antialiasing (kornia's defaults, which ``compute_loss`` uses).  Not differentiated (its input is the HR target)."""
+    antialiasing (kornia's defaults, which ``compute_loss`` and ``LossPipeline`` use).  The result is fp32.  Differentiable: the
+    backward is the adjoint kernel of ``libvsrlab_losses.so``, and an input that is not fp32 gets its gradient in its own dtype."""
     if interpolation != "bilinear" or align_corners not in (None, False) or antialias:
         raise NotImplementedError("HIP resize implements kornia's default: bilinear, align_corners=False, antialias=False")
     _require_gpu(x)
-    if x.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("HIP resize is not differentiated (compute_loss applies it to the target)")
-    h, w = int(size[0]), int(size[1])
-    H, W = x.shape[-2:]
-    x32 = _f32c(x)
-    out = torch.empty(x.shape[:-2] + (h, w), dtype=torch.float32, device=x.device)
-    planes = x32.numel() // (H * W)
-    lib = _lib.load()
-    _lib.check(lib.vsr_resize_bilinear(_ptr(x32), _ptr(out), planes, H, W, h, w, _stream()), "resize_bilinear")
-    return out
+    return _ResizeFn.apply(x, int(size[0]), int(size[1]))
 
 
 def compute_loss(loss_fn, sr, hr, lq=None):

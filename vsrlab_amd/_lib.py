@@ -71,6 +71,16 @@ class WarpTapsDesc(ctypes.Structure):
     _fields_ = [(k, c_int) for k in ("N", "D", "C", "H", "W", "taps", "border", "dtype")] + [("x_nstride", c_longlong)]
 
 
+class BlockDctDesc(ctypes.Structure):
+    """struct VsrBlockDctDesc (include/vsrlab_mixer.h)."""
+    _fields_ = [(k, c_int) for k in ("N", "C", "H", "W", "ps", "dtype")]
+
+
+class AxisMlpDesc(ctypes.Structure):
+    """struct VsrAxisMlpDesc (include/vsrlab_mixer.h)."""
+    _fields_ = [("outer", c_longlong), ("D", c_int), ("inner", c_longlong), ("hidden", c_int), ("dtype", c_int), ("residual", c_int)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -232,6 +242,20 @@ LOSSES_SIGNATURES = {
 }
 LOSSES_EXPORTS = tuple(LOSSES_SIGNATURES)
 
+# libvsrlab_mixer.so (include/vsrlab_mixer.h): the block DCT and the residual axis MLP of the DCT-token MLP-Mixer, likewise
+MIXER_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_mixer.so")
+AXIS_MLP_MAX_D = 48
+AXIS_MLP_MAX_HIDDEN = 1024
+MIXER_SIGNATURES = {
+    "vsr_block_dct_fwd": (c_int, [ctypes.POINTER(BlockDctDesc), _P, _P, _P, _P]),
+    "vsr_block_idct_fwd": (c_int, [ctypes.POINTER(BlockDctDesc), _P, _P, _P, _P]),
+    "vsr_axis_mlp_supported": (c_int, [ctypes.POINTER(AxisMlpDesc)]),
+    "vsr_axis_mlp_scratch_bytes": (c_size_t, [ctypes.POINTER(AxisMlpDesc)]),
+    "vsr_axis_mlp_fwd": (c_int, [ctypes.POINTER(AxisMlpDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "vsr_axis_mlp_bwd": (c_int, [ctypes.POINTER(AxisMlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+MIXER_EXPORTS = tuple(MIXER_SIGNATURES)
+
 # One row per library: its path, the signatures of its ABI, and those of its debug hooks, which only a library that VSRLAB_AMD_LIB
 # names (another build of libvsrlab_hip.so, e.g. a parent commit's for an A/B run) may predate.  _loaded: one slot per library.
 _LIBS = {
@@ -240,6 +264,7 @@ _LIBS = {
     "jpeg": (JPEG_LIB_PATH, JPEG_SIGNATURES, {}),
     "warp_taps": (WARP_TAPS_LIB_PATH, WARP_TAPS_SIGNATURES, {}),
     "losses": (LOSSES_LIB_PATH, LOSSES_SIGNATURES, {}),
+    "mixer": (MIXER_LIB_PATH, MIXER_SIGNATURES, {}),
 }
 _loaded = {}
 
@@ -288,6 +313,11 @@ def load_warp_taps():
 def load_losses():
     """libvsrlab_losses.so."""
     return _load("losses")
+
+
+def load_mixer():
+    """libvsrlab_mixer.so."""
+    return _load("mixer")
 
 
 def check(status, what):

@@ -14,7 +14,8 @@ def install_as_vsrlab(force: bool = False) -> None:
     if "vsrlab" in sys.modules and sys.modules["vsrlab"] is not vsrlab_amd and not force:
         raise RuntimeError("a different `vsrlab` package is already imported; pass force=True to shadow it")
     sys.modules["vsrlab"] = vsrlab_amd
-    for sub in ("core", "core.modules", "core.modules.conv", "core.modules.upsampling", "core.modules.correlation", "core.losses", "vsr", "vsr.models",
+    for sub in ("core", "core.modules", "core.modules.conv", "core.modules.upsampling", "core.modules.correlation", "core.modules.dct_transforms", "core.modules.mlp",
+                "core.schedulers", "core.losses", "vsr", "vsr.models",
                 "vsr.models.RealBasicVSR", "vsr.models.RealBasicVSR.realbasicvsr", "vsr.models.RealBasicVSR.modules",
                 "vsr.models.RealBasicVSR.modules.basicvsr", "vsr.models.RealBasicVSR.modules.spynet",
                 "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.modules",

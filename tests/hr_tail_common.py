@@ -514,16 +514,22 @@ class PmOutput:
         return outs[0] if self.planes == 1 else torch.stack(outs)
 
 
-def run_hip(c: Case, dev):
-    """One hook call on the inputs of `c`; dict output name -> fp32 CPU tensor (the layout of reference()).  A HIP error anywhere in
-    it ends the session: nothing more is started on a card that has faulted."""
+def fault_guarded(c: Case, driver, *args):
+    """driver(c, *args), the one fault guard of the four per-launch drivers (this file's, trunk_common's, spynet_common's and
+    wide_common's): a HIP error anywhere in it ends the session, so nothing more is started on a card that has faulted."""
     try:
-        return _run_hip(c, dev)
+        return driver(c, *args)
     except RuntimeError as e:
         if "HIP" in str(e) or "hip" in str(e):
             import pytest
             pytest.exit(f"GPU fault in {c.name}: {e}", returncode=3)
         raise
+
+
+def run_hip(c: Case, dev):
+    """One hook call on the inputs of `c`; dict output name -> fp32 CPU tensor (the layout of reference()).  A HIP error ends the
+    session (fault_guarded)."""
+    return fault_guarded(c, _run_hip, dev)
 
 
 def _run_hip(c: Case, dev):

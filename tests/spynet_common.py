@@ -718,13 +718,7 @@ MUTATION_NOTES = {
 # --------------------------------------------------------------------------------------------------------------------
 def run_hip(c: Case, dev):
     """One hook call on the inputs of `c`; dict output name -> fp32 CPU tensor in reference()'s layout.  A HIP error ends the session."""
-    try:
-        return _run_hip(c, dev)
-    except RuntimeError as e:
-        if "HIP" in str(e) or "hip" in str(e):
-            import pytest
-            pytest.exit(f"GPU fault in {c.name}: {e}", returncode=3)
-        raise
+    return T.fault_guarded(c, _run_hip, dev)
 
 
 def _pad_channels(t, cp):

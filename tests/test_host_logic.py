@@ -116,6 +116,37 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert loaded.vsr_status_string(-4) == b"workspace too small"
 
 
+def test_debug_signatures_agree_with_the_hooks_one_declaration():
+    """csrc/debug_hooks.h is what the compiler holds every hook's definition (and the host-check programs' calls) to; the ctypes rows
+    of _lib.DEBUG_SIGNATURES must say the same, position by position.  No library and no GPU: the header is read as text."""
+    from vsrlab_amd import _lib
+    text = open(os.path.join(ROOT, "vsrlab_amd", "csrc", "debug_hooks.h")).read()
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+    decls = re.findall(r"\bint\s+(vsr_debug_\w+)\s*\(([^)]*)\)\s*;", text)
+    names = [n for n, _ in decls]
+    assert len(names) == len(set(names)) == 38, sorted(n for n in names if names.count(n) > 1)
+    assert set(names) == set(_lib.DEBUG_SIGNATURES) | set(_lib.OTHER_DEBUG_EXPORTS), set(names) ^ (set(_lib.DEBUG_SIGNATURES) | set(_lib.OTHER_DEBUG_EXPORTS))
+
+    def c_class(param):
+        if "*" in param:
+            return "pointer"
+        for words, cls in (("long long", ctypes.c_longlong), ("float", ctypes.c_float), ("double", ctypes.c_double), ("int", ctypes.c_int),
+                           ("unsigned", ctypes.c_int)):
+            if re.search(rf"\b{words}\b", param):
+                return cls
+        raise AssertionError(f"unclassified parameter {param!r}")
+
+    def row_class(t):
+        return "pointer" if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer) else t
+
+    for name, params in decls:
+        if name not in _lib.DEBUG_SIGNATURES:
+            continue
+        res, args = _lib.DEBUG_SIGNATURES[name]
+        want = [c_class(p) for p in params.split(",") if p.strip() not in ("", "void")]
+        assert res is ctypes.c_int and [row_class(t) for t in args] == want, name
+
+
 def test_workspace_query_and_unsupported_configs_fail_loudly():
     from vsrlab_amd import _lib
     lib = _lib.load()

@@ -447,13 +447,7 @@ def sign_words(n, h, w):
 def run_hip(c: Case, dev, given=None, bits=None):
     """One hook call on the inputs of `c` (`given` replaces some); dict output name -> fp32 CPU tensor in reference()'s layout.  conv cases
     with sign_out also return `_bits` (the device tensor of sign words, to be handed back in as `bits=`).  A HIP error ends the session."""
-    try:
-        return _run_hip(c, dev, given, bits)
-    except RuntimeError as e:
-        if "HIP" in str(e) or "hip" in str(e):
-            import pytest
-            pytest.exit(f"GPU fault in {c.name}: {e}", returncode=3)
-        raise
+    return T.fault_guarded(c, _run_hip, dev, given, bits)
 
 
 def _run_hip(c: Case, dev, given, bits):
@@ -598,14 +592,9 @@ FILL = 0xA5
 def run_chain(c: Case, dev):
     """The forward chain of `blocks` residual blocks, then the matching backward chain reading the sign words the forward one wrote:
     images, packed weights, biases, sign words and the sync block are slots of ONE allocation with sentinel gaps, addressed as
-    256-byte offsets from its base.  dict image name -> (N, 64, H, W) fp32 CPU: what each layer stored (and the two given images)."""
-    try:
-        return _run_chain(c, dev)
-    except RuntimeError as e:
-        if "HIP" in str(e) or "hip" in str(e):
-            import pytest
-            pytest.exit(f"GPU fault in {c.name}: {e}", returncode=3)
-        raise
+    256-byte offsets from its base.  dict image name -> (N, 64, H, W) fp32 CPU: what each layer stored (and the two given images).
+    A HIP error ends the session."""
+    return T.fault_guarded(c, _run_chain, dev)
 
 
 def _run_chain(c: Case, dev):

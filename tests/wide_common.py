@@ -656,13 +656,7 @@ class PmOut:
 
 def run_hip(c: Case, dev, given=None):
     """One hook call; dict output name -> fp32 CPU tensor.  A HIP error anywhere in it ends the session."""
-    try:
-        return _run_hip(c, dev, given)
-    except RuntimeError as e:
-        if "HIP" in str(e) or "hip" in str(e):
-            import pytest
-            pytest.exit(f"GPU fault in {c.name}: {e}", returncode=3)
-        raise
+    return T.fault_guarded(c, _run_hip, dev, given)
 
 
 def wpack_elems(dtype, cout, cin, mode):

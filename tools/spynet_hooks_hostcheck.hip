@@ -1,101 +1,15 @@
 // Stand-alone host check of csrc/spynet_hooks.hip: the hooks' argument checks and what they hand to the launch layer, with every device
-// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is replaced by recorders).
+// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is hostcheck_launch_layer.h's
+// recorders).
 //   make -C vsrlab_amd/csrc hooks_hostcheck
 // Exit status 0 and "spynet hostcheck OK": every refusal came back before any pack or launch, and every accepted call reached
 // vsr_launch_conv / vsr_launch_wgrad / vsr_launch_wgrad_reduce / the elementwise launchers with the template sizes of its layer j, cout_real,
 // the mask mode, the strides, the fp32 64-channel split (x_coff / x_ctotal) and the sizes it was given.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "../vsrlab_amd/csrc/recipes.h"
-
-struct ConvCall { int dtype, ks, nsrc, ca, cb, last_planar, cout_t, epi; ConvArgs a; };
-struct WgradCall { int ks, cx, x_planar, cout, dy_planar, nwg; WgradArgs a; };
-struct ReduceCall { int nwg, ks, cx, cout, cout_real, cin_real, I_total, i_off, accumulate; float* gw; float* gb; };
-struct PackCall { int KK, RP, CPd, r_real, c_real, I_total, i_off, mode; void* dst; };
-// an elementwise launch: which one, its pointers in the launcher's own order, its integers in the launcher's own order
-struct EltCall { const char* name; const void* p[6]; long long v[8]; };
-static std::vector<ConvCall> g_conv;
-static std::vector<WgradCall> g_wgrad;
-static std::vector<ReduceCall> g_reduce;
-static std::vector<PackCall> g_pack;
-static std::vector<EltCall> g_elt;
-static int launches() { return (int)(g_conv.size() + g_wgrad.size() + g_reduce.size() + g_elt.size()); }
-static void reset() { g_conv.clear(); g_wgrad.clear(); g_reduce.clear(); g_pack.clear(); g_elt.clear(); }
-
-int vsr_launch_conv(int dtype, int ks, int nsrc, int ca, int cb, int last_planar, int cout_t, int epi, const ConvArgs& a, hipStream_t) {
-    g_conv.push_back({dtype, ks, nsrc, ca, cb, last_planar, cout_t, epi, a}); return VSR_OK;
-}
-int vsr_launch_sign_bits_c64(const void*, void*, int, int, int, hipStream_t) { return VSR_ERR_BADARG; }                                               // no SPyNet hook reaches it
-int vsr_launch_last2_wgrad(const void*, const float*, long long, float*, int, int, int, int, int*, hipStream_t, int) { return VSR_ERR_BADARG; }   // nor this
-int vsr_launch_wgrad(int, int ks, int cx, int x_planar, int cout, int dy_planar, const WgradArgs& a, int nwg, int* nslabs, hipStream_t) {
-    g_wgrad.push_back({ks, cx, x_planar, cout, dy_planar, nwg, a}); *nslabs = nwg; return VSR_OK;
-}
-int vsr_launch_wgrad_reduce(const float*, int nwg, int ks, int cx, int cout, int cout_real, int cin_real, float* gw, int I_total, int i_off, int, int,
-                            float* gb, int accumulate, hipStream_t) {
-    g_reduce.push_back({nwg, ks, cx, cout, cout_real, cin_real, I_total, i_off, accumulate, gw, gb}); return VSR_OK;
-}
-void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride) {
-    const int ncb = cout >= 32 ? cout / 32 : 1, nib = cx >= 32 ? cx / 32 : 1;
-    *coutp = ncb * 32; *cxp = nib * 32; *stride = ks * ks * (*coutp) * (*cxp) + (*coutp);
-}
-int vsr_launch_pack_weights(int, const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int, int, int mode, hipStream_t) {
-    g_pack.push_back({KK, RP, CPd, r_real, c_real, I_total, i_off, mode, dst}); return w && dst ? VSR_OK : VSR_ERR_BADARG;
-}
-int vsr_launch_resize_norm(const float* in, float* out, const float* mean, const float* std, int F, int h, int w, int hu, int wu, hipStream_t) {
-    g_elt.push_back({"resize_norm", {in, out, mean, std}, {F, h, w, hu, wu}}); return VSR_OK;
-}
-int vsr_launch_resize_norm_bwd(const float* dnorm, float* dframes, const float* std, int F, int h, int w, int hu, int wu, hipStream_t) {
-    g_elt.push_back({"resize_norm_bwd", {dnorm, dframes, std}, {F, h, w, hu, wu}}); return VSR_OK;
-}
-int vsr_launch_avgpool2(const float* in, float* out, long long planes, int h, int w, hipStream_t) {
-    g_elt.push_back({"avgpool2", {in, out}, {planes, h, w}}); return VSR_OK;
-}
-int vsr_launch_avgpool2_bwd_add(const float* dcoarse, float* dfine, long long planes, int h, int w, hipStream_t) {
-    g_elt.push_back({"avgpool2_bwd_add", {dcoarse, dfine}, {planes, h, w}}); return VSR_OK;
-}
-int vsr_launch_flow_out(const float* in, float* out, int P, int hu, int wu, int h, int w, hipStream_t) {
-    g_elt.push_back({"flow_out", {in, out}, {P, hu, wu, h, w}}); return VSR_OK;
-}
-int vsr_launch_flow_out_bwd(const float* dout, float* din, int P, int hu, int wu, int h, int w, hipStream_t) {
-    g_elt.push_back({"flow_out_bwd", {dout, din}, {P, hu, wu, h, w}}); return VSR_OK;
-}
-int vsr_launch_add_f32(const float* a, const float* b, float* out, long long n, hipStream_t) {
-    g_elt.push_back({"add_f32", {a, b, out}, {n}}); return VSR_OK;
-}
-int vsr_launch_spynet_prepare(int dtype, const float* frames, const float* flow_prev, float* flow_up, void* x16, int n, int t, int P, int pair_mode, int h, int w,
-                              int level0, hipStream_t) {
-    g_elt.push_back({"prepare", {frames, flow_prev, flow_up, x16}, {dtype, n, t, P, pair_mode, h, w, level0}}); return VSR_OK;
-}
-int vsr_launch_spynet_prepare_bwd(int dtype, const void* dx16, const float* dflow_l, const float* frames, const float* flow_up, float* dflow_prev, float* dframes,
-                                  int n, int t, int P, int pair_mode, int h, int w, hipStream_t) {
-    g_elt.push_back({"prepare_bwd", {dx16, dflow_l, frames, flow_up, dflow_prev, dframes}, {dtype, n, t, P, pair_mode, h, w}}); return VSR_OK;
-}
-int vsr_launch_spynet_dres(int dtype, const float* dflow, const float* res, void* out, int P, int h, int w, hipStream_t) {
-    g_elt.push_back({"dres", {dflow, res, out}, {dtype, P, h, w}}); return VSR_OK;
-}
-
-extern "C" {
-int vsr_debug_spy_conv(int, int, const void*, const float*, const float*, void*, void*, int, const float*, int, int, int, void*);
-int vsr_debug_spy_dgrad(int, int, const void*, const float*, void*, void*, const void*, int, int, int, void*);
-int vsr_debug_spy_wgrad(int, int, const void*, const void*, float*, float*, int, float*, int, int, int, void*);
-int vsr_debug_spy_prepare(int, const float*, const float*, float*, void*, int, int, int, int, int, int, int, void*);
-int vsr_debug_spy_prepare_bwd(int, const void*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, void*);
-int vsr_debug_spy_dres(int, const float*, const float*, void*, int, int, int, void*);
-int vsr_debug_spy_planar(int, const float*, const float*, float*, const float*, const float*, long long, int, int, int, int, void*);
-}
-
-static int g_fail = 0;
-#define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "spynet hostcheck: line %d: %s\n", __LINE__, #cond); ++g_fail; } } while (0)
-// a refusal: the status, and neither a pack nor a launch happened
-#define REFUSED(call, status) do { reset(); EXPECT((call) == (status)); EXPECT(launches() == 0 && g_pack.empty()); } while (0)
-static bool is(const EltCall& e, const char* name) { return std::strcmp(e.name, name) == 0; }
+#define HOSTCHECK_NAME "spynet hostcheck"
+#include "hostcheck_launch_layer.h"
 
 int main() {
-    // real, small buffers: an accepted call hands them to the (stubbed) launch layer only
-    float* f = static_cast<float*>(std::aligned_alloc(256, 1 << 16));
-    for (int i = 0; i < (1 << 14); ++i) f[i] = 0.f;
+    float* f = hostcheck_buffer();
     void* v = f;
     char* cb = reinterpret_cast<char*>(f);
     const int n = 2, h = 8, w = 12, BF = VSR_BF16, FP = VSR_F32;
@@ -262,8 +176,8 @@ int main() {
         if (op == 6) EXPECT(e.p[1] == f + 64 && e.p[2] == f + 128 && e.v[0] == 5LL * h * w);
     }
 
-    std::free(f);
-    if (g_fail) { std::fprintf(stderr, "spynet hostcheck: %d check(s) failed\n", g_fail); return 1; }
-    std::puts("spynet hostcheck OK");
-    return 0;
+    // no SPyNet hook reaches the sign bits, the streaming conv_last.2 launchers, the chain or the wide launchers
+    EXPECT(never({"sign_bits_c64", "last2_wgrad", "last2_dgrad", "conv3x3_chain", "conv_wide", "pack_wide", "pack_wide2", "wgrad_pairs", "wgrad_reduce_s2",
+                  "up2_fwd", "up2_bwd", "mask", "pool_fwd", "pool_bwd", "tap_l1", "tap_sum"}));
+    return hostcheck_finish(f);
 }

@@ -1,69 +1,15 @@
 // Stand-alone host check of csrc/trunk_hooks.hip: the hooks' argument checks and what they hand to the launch layer, with every device
-// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is replaced by recorders).
+// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is hostcheck_launch_layer.h's
+// recorders).
 //   make -C vsrlab_amd/csrc hooks_hostcheck
 // Exit status 0 and "trunk hostcheck OK": every refusal came back before any pack or launch, and every accepted call reached
 // vsr_launch_conv / vsr_launch_wgrad / vsr_launch_wgrad_reduce / vsr_launch_conv3x3_chain with the segment counts, strides, i_off,
 // accumulate flag and layer offsets it was given.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include "../vsrlab_amd/csrc/recipes.h"
-
-struct ConvCall { int ks, nsrc, ca, cb, last_planar, cout_t, epi; ConvArgs a; };
-struct WgradCall { int ks, cx, x_planar, cout, dy_planar, nwg; WgradArgs a; };
-struct ReduceCall { int nwg, ks, cx, cout, cout_real, cin_real, I_total, i_off, accumulate; float* gw; float* gb; };
-struct PackCall { int KK, RP, CPd, r_real, c_real, I_total, i_off, mode; void* dst; };
-static std::vector<ConvCall> g_conv;
-static std::vector<WgradCall> g_wgrad;
-static std::vector<ReduceCall> g_reduce;
-static std::vector<PackCall> g_pack;
-static std::vector<ChainArgs> g_chain;
-static int g_sign = 0;
-static int launches() { return (int)(g_conv.size() + g_wgrad.size() + g_reduce.size() + g_chain.size()) + g_sign; }
-static void reset() { g_conv.clear(); g_wgrad.clear(); g_reduce.clear(); g_pack.clear(); g_chain.clear(); g_sign = 0; }
-
-int vsr_launch_conv(int, int ks, int nsrc, int ca, int cb, int last_planar, int cout_t, int epi, const ConvArgs& a, hipStream_t) {
-    g_conv.push_back({ks, nsrc, ca, cb, last_planar, cout_t, epi, a}); return VSR_OK;
-}
-int vsr_launch_sign_bits_c64(const void* x, void* bits, int, int, int, hipStream_t) { ++g_sign; return x && bits ? VSR_OK : VSR_ERR_BADARG; }
-int vsr_launch_last2_wgrad(const void*, const float*, long long, float*, int, int, int, int, int*, hipStream_t, int) { return VSR_ERR_BADARG; }   // no trunk hook reaches it
-int vsr_launch_wgrad(int, int ks, int cx, int x_planar, int cout, int dy_planar, const WgradArgs& a, int nwg, int* nslabs, hipStream_t) {
-    g_wgrad.push_back({ks, cx, x_planar, cout, dy_planar, nwg, a}); *nslabs = nwg; return VSR_OK;
-}
-int vsr_launch_wgrad_reduce(const float*, int nwg, int ks, int cx, int cout, int cout_real, int cin_real, float* gw, int I_total, int i_off, int, int,
-                            float* gb, int accumulate, hipStream_t) {
-    g_reduce.push_back({nwg, ks, cx, cout, cout_real, cin_real, I_total, i_off, accumulate, gw, gb}); return VSR_OK;
-}
-void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride) {
-    const int ncb = cout >= 32 ? cout / 32 : 1, nib = cx >= 32 ? cx / 32 : 1;
-    *coutp = ncb * 32; *cxp = nib * 32; *stride = ks * ks * (*coutp) * (*cxp) + (*coutp);
-}
-int vsr_launch_pack_weights(int, const float* w, void* dst, int KK, int RP, int CPd, int r_real, int c_real, int I_total, int i_off, int, int, int mode, hipStream_t) {
-    g_pack.push_back({KK, RP, CPd, r_real, c_real, I_total, i_off, mode, dst}); return w && dst ? VSR_OK : VSR_ERR_BADARG;
-}
-int vsr_launch_conv3x3_chain(const ChainArgs& a, int num_cus, hipStream_t) { g_chain.push_back(a); return num_cus >= 1 ? VSR_OK : VSR_ERR_BADARG; }
-
-extern "C" {
-int vsr_debug_trunk_conv(int, int, int, int, const void*, const float*, const float*, void*, void*, int, float, const void*, const void*, int, void*, void*, int, int,
-                         int, int, int, void*);
-int vsr_debug_trunk_stem(int, int, int, const void*, const float*, long long, const float*, const float*, void*, void*, int, float, int, int, int, void*);
-int vsr_debug_trunk_stem_dgrad(int, int, int, const void*, const float*, void*, void*, float*, long long, int, int, int, int, void*);
-int vsr_debug_trunk_point(int, int, int, const void*, const void*, const float*, const float*, void*, void*, void*, int, int, int, void*);
-int vsr_debug_trunk_wgrad_cc(int, int, int, const void* const*, const void* const*, int, float*, int, int, float*, int, float*, int, int, int, void*);
-int vsr_debug_trunk_stem_wgrads(int, int, int, const float* const*, long long, const void* const*, int, const void* const*, const void* const*, int, float*, float*,
-                                int, float*, int, int, int, void*);
-int vsr_debug_trunk_chain(int, int, void*, void*, const unsigned*, int, const float* const*, int, int, int, int, void*);
-}
-
-static int g_fail = 0;
-#define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "trunk hostcheck: line %d: %s\n", __LINE__, #cond); ++g_fail; } } while (0)
-// a refusal: the status, and neither a pack nor a launch happened
-#define REFUSED(call, status) do { reset(); EXPECT((call) == (status)); EXPECT(launches() == 0 && g_pack.empty()); } while (0)
+#define HOSTCHECK_NAME "trunk hostcheck"
+#include "hostcheck_launch_layer.h"
 
 int main() {
-    // real, small buffers: an accepted call hands them to the (stubbed) launch layer only
-    float* f = static_cast<float*>(std::aligned_alloc(256, 1 << 16));
-    for (int i = 0; i < (1 << 14); ++i) f[i] = 0.f;
+    float* f = hostcheck_buffer();
     void* v = f;
     char* cb = reinterpret_cast<char*>(f);
     const int n = 2, h = 8, w = 12, BF = VSR_BF16, FP = VSR_F32;
@@ -235,8 +181,7 @@ int main() {
     EXPECT(g_chain[0].layer[0].sbits == 7 && g_chain[0].layer[0].bias == NONE && g_chain[0].layer[0].variant == CHAIN_MASK && g_chain[0].layer[1].res == 9 &&
            g_chain[0].layer[2].sbits == 8 && g_chain[0].layer[2].src == 11 && g_chain[0].layer[2].dst == 12);
 
-    std::free(f);
-    if (g_fail) { std::fprintf(stderr, "trunk hostcheck: %d check(s) failed\n", g_fail); return 1; }
-    std::puts("trunk hostcheck OK");
-    return 0;
+    // no trunk hook reaches the streaming conv_last.2 launchers, the elementwise or the wide ones
+    EXPECT(never({"last2_wgrad", "last2_dgrad", "conv_wide", "pack_wide", "pack_wide2", "wgrad_pairs", "wgrad_reduce_s2"}) && g_elt.empty());
+    return hostcheck_finish(f);
 }

@@ -1,103 +1,16 @@
 // Stand-alone host check of csrc/wide_hooks.hip: the hooks' argument checks and what they hand to the launch layer, with every device
-// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is replaced by recorders).
+// launch stubbed, for a run under ASan / UBSan on a machine without a GPU (the launch layer below the hooks is hostcheck_launch_layer.h's
+// recorders).
 //   make -C vsrlab_amd/csrc hooks_hostcheck        (or the target wide_hostcheck alone)
 // Exit status 0 and "wide hostcheck OK": every refusal came back before any pack or launch; every accepted vsr_debug_wide_conv reached the
 // pack of its mode and vsr_launch_conv_wide with the slices, output blocks, steps, image sizes, epilogue operands and max_wg of its mode;
 // vsr_debug_wide_wgrad reached vsr_launch_wgrad_pairs with the ksplit of WideCtx::pair_ksplit for every layer geometry at 1, 8 and 200
 // tiles (bf16), or the pair-by-pair path with each pair's parity view, channel slices and destination block (fp32).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include "../vsrlab_amd/csrc/wide_recipes.h"
-
-struct WideCall { int dtype; VsrWideConv c; };
-struct PackCall { int w2, dtype, cout, cin, mode; void* dst; };
-struct PairsCall { int nsl, ncob, views, ksplit, cin_total; float* gw; WgradArgs a; };
-struct WgradCall { int ks, cx, x_planar, cout, dy_planar, nwg; WgradArgs a; };
-struct ReduceCall { int s2, nwg, cin_total, co0, ci0, view, I_total, i_off, accumulate; float* gw; };
-struct EltCall { const char* name; const void* p[4]; long long v[8]; float f; };
-static std::vector<WideCall> g_wide;
-static std::vector<PackCall> g_pack;
-static std::vector<PairsCall> g_pairs;
-static std::vector<WgradCall> g_wgrad;
-static std::vector<ReduceCall> g_reduce;
-static std::vector<EltCall> g_elt;
-static int launches() { return (int)(g_wide.size() + g_pairs.size() + g_wgrad.size() + g_reduce.size() + g_elt.size()); }
-static void reset() { g_wide.clear(); g_pack.clear(); g_pairs.clear(); g_wgrad.clear(); g_reduce.clear(); g_elt.clear(); }
-
-int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t) { g_wide.push_back({dtype, c}); return VSR_OK; }
-long long vsr_wide_pack_elems(int cout, int cin, int mode) { return ((mode == 1 || mode == 3) ? 4LL : 1LL) * (cout / 64) * (cin / 64) * 9 * 4096; }
-long long vsr_wide2_pack_elems(int cout, int cin, int mode) {
-    const bool s2 = mode == 1 || mode == 3;
-    const int nsl = (mode == 0 || mode == 1 ? cin : cout) / 64, rows = (mode == 0 || mode == 1) ? cout : cin;
-    const bool ks = (rows & 127) != 0;
-    const int tps = s2 ? 4 : 9;
-    return (long long)(rows / (ks ? 64 : 128)) * (mode == 3 ? 4 : 1) * nsl * (mode == 1 ? 4 : 1) * (ks ? (tps + 1) / 2 : tps) * 8192;
-}
-int vsr_launch_pack_wide2(const float*, void* dst, int cout, int cin, int mode, hipStream_t) { g_pack.push_back({1, VSR_BF16, cout, cin, mode, dst}); return VSR_OK; }
-int vsr_launch_pack_wide(int dtype, const float*, void* dst, int cout, int cin, int mode, hipStream_t) { g_pack.push_back({0, dtype, cout, cin, mode, dst}); return VSR_OK; }
-void vsr_wide2_grid(int ncob, int out_step, int N, int H, int W, int max_wg, int num_cus, int* nwx, int* cols, int* tiles) {
-    *nwx = max_wg; *cols = ncob * out_step; *tiles = N * H * W + num_cus;      // a recorder: the real one is conv_wide.hip's
-}
-int vsr_launch_wgrad_pairs(int, const WgradArgs& a, int nsl, int ncob, int views, int ksplit, float* gw, int cin_total, hipStream_t) {
-    g_pairs.push_back({nsl, ncob, views, ksplit, cin_total, gw, a}); return VSR_OK;
-}
-int vsr_launch_wgrad(int, int ks, int cx, int x_planar, int cout, int dy_planar, const WgradArgs& a, int nwg, int* nslabs, hipStream_t) {
-    g_wgrad.push_back({ks, cx, x_planar, cout, dy_planar, nwg, a}); *nslabs = nwg; return VSR_OK;
-}
-int vsr_launch_last2_wgrad(const void*, const float*, long long, float*, int, int, int, int, int*, hipStream_t, int) { return VSR_ERR_BADARG; }   // no wide hook reaches it
-int vsr_launch_wgrad_reduce(const float*, int nwg, int, int, int, int, int, float* gw, int I_total, int i_off, int, int, float*, int accumulate, hipStream_t) {
-    g_reduce.push_back({0, nwg, 0, 0, 0, -1, I_total, i_off, accumulate, gw}); return VSR_OK;
-}
-int vsr_launch_wgrad_reduce_s2(const float*, int nwg, int, float* gw, int cin_total, int co0, int ci0, int view, hipStream_t) {
-    g_reduce.push_back({1, nwg, cin_total, co0, ci0, view, 0, 0, 1, gw}); return VSR_OK;
-}
-void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride) {
-    *coutp = cout; *cxp = cx; *stride = ks * ks * cout * cx + cout;
-}
-int vsr_launch_up2_fwd(int dtype, const void* a, const void* b, void* out, int N, int H, int W, int C, hipStream_t) {
-    g_elt.push_back({"up2_fwd", {a, b, out}, {dtype, N, H, W, C}, 0.f}); return VSR_OK;
-}
-int vsr_launch_up2_bwd(int dtype, const void* dout, void* din, void* dmask, const void* m, float slope, int N, int H, int W, int C, hipStream_t) {
-    g_elt.push_back({"up2_bwd", {dout, din, dmask, m}, {dtype, N, H, W, C}, slope}); return VSR_OK;
-}
-int vsr_launch_mask_pm(int dtype, const void* g, const void* m, void* out, float slope, long long elems, hipStream_t) {
-    g_elt.push_back({"mask", {g, m, out}, {dtype, elems}, slope}); return VSR_OK;
-}
-int vsr_launch_maxpool2_fwd(int dtype, const void* in, void* out, int N, int Hi, int Wi, int C, hipStream_t) {
-    g_elt.push_back({"pool_fwd", {in, out}, {dtype, N, Hi, Wi, C}, 0.f}); return VSR_OK;
-}
-int vsr_launch_maxpool2_bwd(int dtype, const void* a, const void* dp, void* g, int N, int Hi, int Wi, int C, hipStream_t) {
-    g_elt.push_back({"pool_bwd", {a, dp, g}, {dtype, N, Hi, Wi, C}, 0.f}); return VSR_OK;
-}
-int vsr_launch_tap_l1(int dtype, const void* s, const void* h, void* g, float scale, int N, int H, int W, int C, double* partial, int nblocks, hipStream_t) {
-    g_elt.push_back({"tap_l1", {s, h, g, partial}, {dtype, N, H, W, C, nblocks}, scale}); return VSR_OK;
-}
-int vsr_launch_tap_sum(const double* partial, double* sums, int N, const int* nb, hipStream_t) {
-    g_elt.push_back({"tap_sum", {partial, sums}, {N, nb[0], nb[1], nb[2], nb[3], nb[4]}, 0.f}); return VSR_OK;
-}
-
-extern "C" {
-int vsr_debug_wide_conv(int, int, int, int, const void*, const float*, const float*, void*, long long, void*, int, float, void*, const void*, const void*, int, int, int,
-                        int, void*);
-int vsr_debug_wide_wgrad(int, int, int, int, const void*, const void*, float*, float*, long long, int, int, int, void*);
-int vsr_debug_wide_up2_fwd(int, const void*, const void*, void*, int, int, int, int, void*);
-int vsr_debug_wide_up2_bwd(int, const void*, void*, void*, const void*, float, int, int, int, int, void*);
-int vsr_debug_wide_mask(int, const void*, const void*, void*, float, long long, void*);
-int vsr_debug_vgg_pool(int, int, const void*, const void*, void*, int, int, int, int, void*);
-int vsr_debug_vgg_tap(int, const void*, void*, int, float, double*, double*, int, int, int, int, void*);
-int vsr_debug_wide_grid(int, int, int, int, int, int, int, int*);
-}
-
-static int g_fail = 0;
-#define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "wide hostcheck: line %d: %s\n", __LINE__, #cond); ++g_fail; } } while (0)
-#define REFUSED(call, status) do { reset(); EXPECT((call) == (status)); EXPECT(launches() == 0 && g_pack.empty()); } while (0)
-static bool is(const EltCall& e, const char* name) { return std::strcmp(e.name, name) == 0; }
+#define HOSTCHECK_NAME "wide hostcheck"
+#include "hostcheck_launch_layer.h"
 
 int main() {
-    float* f = static_cast<float*>(std::aligned_alloc(256, 1 << 16));
-    for (int i = 0; i < (1 << 14); ++i) f[i] = 0.f;
+    float* f = hostcheck_buffer();
     void* v = f;
     char* cb = reinterpret_cast<char*>(f);
     double* dd = reinterpret_cast<double*>(cb + 16384);
@@ -279,8 +192,8 @@ int main() {
     REFUSED(vsr_debug_wide_grid(2, 1, n, h, w, 0, 256, nullptr), VSR_ERR_BADARG);
     EXPECT(vsr_debug_wide_grid(4, 2, n, h, w, 3, 256, out) == VSR_OK && out[0] == 3 && out[1] == 8 && out[2] == n * h * w + 256);
 
-    std::free(f);
-    if (g_fail) { std::fprintf(stderr, "wide hostcheck: %d check(s) failed\n", g_fail); return 1; }
-    std::puts("wide hostcheck OK");
-    return 0;
+    // no wide hook reaches the BasicVSR side's conv, pack, sign-bit, streaming conv_last.2, chain or SPyNet launchers
+    EXPECT(never({"conv", "pack_weights", "sign_bits_c64", "last2_wgrad", "last2_dgrad", "conv3x3_chain", "resize_norm", "resize_norm_bwd", "avgpool2",
+                  "avgpool2_bwd_add", "flow_out", "flow_out_bwd", "add_f32", "prepare", "prepare_bwd", "dres"}));
+    return hostcheck_finish(f);
 }

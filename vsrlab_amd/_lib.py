@@ -158,7 +158,8 @@ EXPORTS = tuple(_SIGNATURES)
 # Test hooks of csrc/hr_tail_hooks.hip and csrc/trunk_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in
 # EXPORTS, like the other vsr_debug_* entries, whose argument types the tests that call them set by hand).  These fourteen have long
 # mixed int / long long / float / pointer lists and three callers each (a host test, a GPU test, the driver), so their types are stated
-# once, here; load() applies them.
+# once, here; load() applies them.  csrc/debug_hooks.h declares every hook once for the compiler, and tests/test_host_logic.py holds
+# these rows to it, position by position.
 # OTHER_DEBUG_EXPORTS: the library's remaining vsr_debug_* symbols.  EXPORTS + OTHER_DEBUG_EXPORTS + DEBUG_SIGNATURES is every
 # `vsr_` symbol the product library exports (tests/test_hr_tail_host.py enumerates its dynamic symbol table against this).
 OTHER_DEBUG_EXPORTS = ("vsr_debug_chain_inject_error", "vsr_debug_chain_item", "vsr_debug_chain_timeouts", "vsr_debug_chain_timing_begin",

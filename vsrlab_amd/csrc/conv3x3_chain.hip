@@ -40,6 +40,7 @@
 // conv3x3_persist.hip: conv3x3_c64_tile.h, described there.  Here: hand-out, flags, publish, the sc1 memory operations.
 #include "conv3x3_c64_tile.h"
 #include "kernels.h"
+#include "debug_hooks.h"
 #include <atomic>
 #include <type_traits>
 

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "elt.h"
 #include "kernels.h"
+#include "debug_hooks.h"
 #include "../../include/vsrlab_hip.h"
 
 namespace {
@@ -743,18 +744,6 @@ __global__ void up2_bwd_kernel(const T* __restrict__ dout, T* __restrict__ din, 
     }
 }
 
-// out = a + b  (blocked tensors of identical geometry: plain elementwise over the padded image)
-template <typename T>
-__global__ void add_pm_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long long n8) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        float f[8], g[8];
-        ld8<T>(a + i * 8, f); ld8<T>(b + i * 8, g);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] += g[j];
-        st8<T>(out + i * 8, f);
-    }
-}
-
 // out = g * (m > 0 ? 1 : slope)
 template <typename T>
 __global__ void mask_pm_kernel(const T* __restrict__ g, const T* __restrict__ m, T* __restrict__ out, float slope, long long n8) {
@@ -981,24 +970,14 @@ int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t st) {
     const long long gz = (long long)c.N * nph * c.ncob;
     if (gz > 65535) return VSR_ERR_UNSUPPORTED;
     dim3 grid(cdiv(c.W, TW), cdiv(c.H, TH), (unsigned)gz);
-    if (dtype == VSR_BF16) {
-        constexpr int LDS = NPIX * 8 * 16 + 2 * 64 * 8 * 16;
-        hipLaunchKernelGGL(conv_wide_kernel<bf16_t>, grid, dim3(NTHREADS), LDS, st, a);
-    } else if (dtype == VSR_F32) {
-        constexpr int LDS = NPIX * 8 * 32 + 2 * 64 * 8 * 32;       // 87,040 + 32,768 = 119,808 B
-        static VsrDevOnce once;
-        { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(conv_wide_kernel<float>), LDS); if (rc != VSR_OK) return rc; }
-        hipLaunchKernelGGL(conv_wide_kernel<float>, grid, dim3(NTHREADS), LDS, st, a);
-    } else {
-        return VSR_ERR_BADARG;
-    }
+    if (dtype == VSR_BF16) return VSR_ERR_UNSUPPORTED;      // bf16 runs on conv_wide2 (wpack2) alone: WideCtx::wide never hands it this image
+    if (dtype != VSR_F32) return VSR_ERR_BADARG;
+    constexpr int LDS = NPIX * 8 * 32 + 2 * 64 * 8 * 32;       // 87,040 + 32,768 = 119,808 B
+    static VsrDevOnce once;
+    { const int rc = vsr_set_max_dynamic_lds(once, reinterpret_cast<const void*>(conv_wide_kernel<float>), LDS); if (rc != VSR_OK) return rc; }
+    hipLaunchKernelGGL(conv_wide_kernel<float>, grid, dim3(NTHREADS), LDS, st, a);
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
-}
-
-long long vsr_wide_pack_elems(int cout, int cin, int mode) {
-    const long long blocks = (mode == 1 || mode == 3) ? 4LL * (cout / 64) * (cin / 64) : (long long)(cout / 64) * (cin / 64);
-    return blocks * 9 * 4096;
 }
 
 int vsr_launch_pack_wide(int dtype, const float* w, void* dst, int cout, int cin, int mode, hipStream_t st) {
@@ -1010,16 +989,6 @@ int vsr_launch_pack_wide(int dtype, const float* w, void* dst, int cout, int cin
     else return VSR_ERR_BADARG;
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;
-}
-
-// rows = output channels of the launch (mode 0/1: cout, mode 2/3: cin); a multiple of 128 -> 128-row slabs, else the K-split image
-long long vsr_wide2_pack_elems(int cout, int cin, int mode) {
-    const bool s2 = mode == 1 || mode == 3;
-    const int nsl = (mode == 0 || mode == 1 ? cin : cout) / 64, rows = (mode == 0 || mode == 1) ? cout : cin;
-    const bool ks = (rows & 127) != 0;
-    const int tps = s2 ? 4 : 9;
-    const long long cols = (long long)(rows / (ks ? 64 : 128)) * (mode == 3 ? 4 : 1);
-    return cols * nsl * (mode == 1 ? 4 : 1) * (ks ? (tps + 1) / 2 : tps) * 8192;
 }
 
 int vsr_launch_pack_wide2(const float* w, void* dst, int cout, int cin, int mode, hipStream_t st) {
@@ -1055,15 +1024,6 @@ int vsr_launch_up2_bwd(int dtype, const void* dout, void* din, void* dmask, cons
     const dim3 grid(cdiv(pm_ws(W) * 32 * (C / 8), 256), H, N);
     if (dtype == VSR_BF16) hipLaunchKernelGGL(up2_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dout, (bf16_t*)din, (bf16_t*)dmask, (const bf16_t*)m, slope, N, H, W, C);
     else if (dtype == VSR_F32) hipLaunchKernelGGL(up2_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)dout, (float*)din, (float*)dmask, (const float*)m, slope, N, H, W, C);
-    else return VSR_ERR_BADARG;
-    HIP_CHECK_RET(hipGetLastError());
-    return VSR_OK;
-}
-
-int vsr_launch_add_pm(int dtype, const void* a, const void* b, void* out, long long elems, hipStream_t st) {
-    const long long n8 = elems / 8;
-    if (dtype == VSR_BF16) hipLaunchKernelGGL(add_pm_kernel<bf16_t>, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n8);
-    else if (dtype == VSR_F32) hipLaunchKernelGGL(add_pm_kernel<float>, dim3(grid_for(n8)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n8);
     else return VSR_ERR_BADARG;
     HIP_CHECK_RET(hipGetLastError());
     return VSR_OK;

@@ -3,6 +3,7 @@
 // Argument checks and launches only: no kernel lives here.  tests/test_hr_tail_gpu.py compares every hook with an fp64 restatement.
 //   w: fp32 OIHW; *_pm: blocked pixel-major, 64 channels, element type of `dtype`; wpack / bias_pack / sign_scratch / slab: caller scratch.
 #include "recipes.h"
+#include "debug_hooks.h"
 
 extern "C" {
 

@@ -22,7 +22,13 @@ struct ChainArgs {
 };
 size_t vsr_chain_sync_bytes(int nlayers, int N, int H, int W);
 int vsr_launch_conv3x3_chain(const ChainArgs& a, int num_cus, hipStream_t st);
-void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride);
+// slab layout of a weight-gradient launch: padded rows / columns of a partial, floats between partials
+inline void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride) {
+    const int ncb = cout >= 32 ? cout / 32 : 1, nib = cx >= 32 ? cx / 32 : 1;
+    *coutp = ncb * 32;
+    *cxp = nib * 32;
+    *stride = ks * ks * (*coutp) * (*cxp) + (*coutp);
+}
 int vsr_launch_wgrad(int dtype, int ks, int cx, int x_planar, int cout, int dy_planar, const WgradArgs& a, int nwg,
                      int* nslabs, hipStream_t st);      // *nslabs: partial slabs written (what the reduction sums)
 int vsr_launch_wgrad_reduce(const float* slab, int nwg, int ks, int cx, int cout, int cout_real, int cin_real, float* gw,
@@ -90,15 +96,27 @@ int vsr_launch_conv_wide(int dtype, const VsrWideConv& c, hipStream_t st);
 // the grid of conv_wide2 for a launch with `ncob` 64-channel output blocks: *cols output columns (phases x 128-channel blocks, or
 // 64-channel blocks of the K-split form) of *nwx workgroups each over *tiles 8 x 32 tiles.  Host only.  max_wg as VsrWideConv's
 void vsr_wide2_grid(int ncob, int out_step, int N, int H, int W, int max_wg, int num_cus, int* nwx, int* cols, int* tiles);
-long long vsr_wide_pack_elems(int cout, int cin, int mode);
-long long vsr_wide2_pack_elems(int cout, int cin, int mode);
+// elements of the weight image of vsr_launch_pack_wide ...
+inline long long vsr_wide_pack_elems(int cout, int cin, int mode) {
+    const long long blocks = (mode == 1 || mode == 3) ? 4LL * (cout / 64) * (cin / 64) : (long long)(cout / 64) * (cin / 64);
+    return blocks * 9 * 4096;
+}
+// ... and of vsr_launch_pack_wide2: rows = output channels of the launch (mode 0/1: cout, mode 2/3: cin); a multiple of 128 -> 128-row
+// slabs, else the K-split image
+inline long long vsr_wide2_pack_elems(int cout, int cin, int mode) {
+    const bool s2 = mode == 1 || mode == 3;
+    const int nsl = (mode == 0 || mode == 1 ? cin : cout) / 64, rows = (mode == 0 || mode == 1) ? cout : cin;
+    const bool ks = (rows & 127) != 0;
+    const int tps = s2 ? 4 : 9;
+    const long long cols = (long long)(rows / (ks ? 64 : 128)) * (mode == 3 ? 4 : 1);
+    return cols * nsl * (mode == 1 ? 4 : 1) * (ks ? (tps + 1) / 2 : tps) * 8192;
+}
 int vsr_launch_pack_wide2(const float* w, void* dst, int cout, int cin, int mode, hipStream_t st);
 int vsr_launch_pack_wide(int dtype, const float* w, void* dst, int cout, int cin, int mode, hipStream_t st);
 int vsr_launch_wgrad_reduce_s2(const float* slab, int nwg, int slab_stride, float* gw, int cin_total, int co0, int ci0, int view, hipStream_t st);
 int vsr_launch_up2_fwd(int dtype, const void* a, const void* b, void* out, int N, int H, int W, int C, hipStream_t st);
 int vsr_launch_up2_bwd(int dtype, const void* dout, void* din, void* dmask, const void* m, float slope, int N, int H, int W, int C, hipStream_t st);
 int vsr_launch_mask_pm(int dtype, const void* g, const void* m, void* out, float slope, long long elems, hipStream_t st);
-int vsr_launch_add_pm(int dtype, const void* a, const void* b, void* out, long long elems, hipStream_t st);
 
 // ---- VGG19's own kernels (perceptual_engine.hip), on blocked pixel-major (N, Hi, Wi, C) ----
 int vsr_launch_maxpool2_fwd(int dtype, const void* in, void* out, int N, int Hi, int Wi, int C, hipStream_t st);

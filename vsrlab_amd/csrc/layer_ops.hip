@@ -1,6 +1,7 @@
 // The per-op C ABI: one layer (or one elementwise step) per call on the caller's buffers, through the same launch recipes as the
 // engines.  Argument checks and launches only.
 #include "recipes.h"
+#include "debug_hooks.h"
 
 constexpr int C64 = 64;         // the fixed width of the vsr_conv3x3_c64_* entries and of vsr_conv_layer_bwd's scratch layout
 

@@ -236,7 +236,7 @@ struct PCtx {
     // 3x3 stride-1 conv at >= 64 channels on conv_wide (fp32) / conv_wide2 (bf16).  aux: ReLU mask source (slope 0)
     int wide(int k, bool dgrad, const void* x, void* y, int act, const void* aux) const {
         const int lv = L_LV[k], xC = dgrad ? L_CO[k] : L_CI[k], yC = dgrad ? L_CI[k] : L_CO[k];
-        return wc().wide(x, xC, p.Hl[lv], p.Wl[lv], 1, p.Hl[lv], p.Wl[lv], at(dgrad ? p.wd[k] : p.wf[k]), dtype == VSR_BF16, dgrad ? nullptr : fat(p.bias[k]),
+        return wc().wide(x, xC, p.Hl[lv], p.Wl[lv], 1, p.Hl[lv], p.Wl[lv], at(dgrad ? p.wd[k] : p.wf[k]), dgrad ? nullptr : fat(p.bias[k]),
                          y, yC, 1, act, 0.f, nullptr, nullptr, nullptr, aux);
     }
     int pool_fwd(int lv, int C, const void* in, void* out) const { return wc().pool_fwd(in, out, p.Hl[lv], p.Wl[lv], C); }

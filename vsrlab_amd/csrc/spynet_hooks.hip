@@ -7,6 +7,7 @@
 //   SPY_DK[j] (the gradient of its output); planar tensors are fp32.  wpack: 49 * 64 * 64 elements; slab:
 //   vsr_conv3x3_c64_wgrad_slab_floats() floats.
 #include "recipes.h"
+#include "debug_hooks.h"
 
 namespace {
 bool bad_layer(int j) { return j < 0 || j >= NSPY; }

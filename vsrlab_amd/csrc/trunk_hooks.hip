@@ -5,6 +5,7 @@
 //   wpack / slab: caller scratch; x[] / dy[] of the weight gradients: HOST arrays of device pointers, one per segment.
 // Sign bits and chains exist on the persistent 64-channel bf16 kernels only: VSR_ERR_UNSUPPORTED at another width or in fp32.
 #include "recipes.h"
+#include "debug_hooks.h"
 
 namespace {
 bool bad_width(int C) { return C != 16 && C != 32 && C != 64; }

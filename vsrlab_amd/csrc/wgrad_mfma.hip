@@ -745,14 +745,6 @@ extern "C" int vsr_debug_read_wclk(unsigned long long* host_out) {
 
 int vsr_launch_wgrad7x7_pc(int cx, int cout, const WgradArgs& a, int max_slabs, int* nslabs, hipStream_t st);   // wgrad7x7_pc.hip
 
-// slab layout helper shared with the engine
-void vsr_wgrad_slab_dims(int ks, int cx, int cout, int* coutp, int* cxp, int* stride) {
-    const int ncb = cout >= 32 ? cout / 32 : 1, nib = cx >= 32 ? cx / 32 : 1;
-    *coutp = ncb * 32;
-    *cxp = nib * 32;
-    *stride = ks * ks * (*coutp) * (*cxp) + (*coutp);
-}
-
 int vsr_launch_wgrad(int dtype, int ks, int cx, int x_planar, int cout, int dy_planar,
                      const WgradArgs& a, int nwg, int* nslabs, hipStream_t st) {
     if (a.nseg < 1 || a.nseg > VSR_WG_MAXSEG || nwg < 1 || !nslabs) return VSR_ERR_BADARG;

@@ -3,9 +3,10 @@
 // call, with the weight image the engines' pack step makes.  Argument checks and launches only: no kernel lives here.
 // tests/test_wide_gpu.py compares every hook with an fp64 restatement.  (vsr_debug_disc_plan sits beside the plan it reads, in
 // disc_engine.hip; vsr_debug_wide2_set_max_wg beside the launcher, in conv_wide.hip.)
-//   *_pm: blocked pixel-major of the element type of `dtype`; w: fp32 OIHW.  add_pm and the bf16 instance of the generic conv_wide_kernel
-//   are launched by no engine and by no hook.
+//   *_pm: blocked pixel-major of the element type of `dtype`; w: fp32 OIHW.  bf16 runs on conv_wide2_kernel, fp32 on the generic
+//   conv_wide_kernel: the dtype alone picks the weight image and the kernel (vsr_launch_conv_wide refuses the generic image in bf16).
 #include "wide_recipes.h"
+#include "debug_hooks.h"
 
 namespace {
 bool bad_ch(int c) { return c < 64 || (c & 63); }
@@ -26,13 +27,13 @@ int vsr_debug_wide_conv(int dtype, int mode, int cout, int cin, const void* x_pm
     if (bad_dtype(dtype) || mode < 0 || mode > 3 || bad_ch(cout) || bad_ch(cin) || !x_pm || !w || !wpack || !y_pm || bad_dims(N, H, W) || max_wg < 0 ||
         (act != ACT_NONE && act != ACT_RELU && act != ACT_LEAKY))
         return VSR_ERR_BADARG;
-    const bool w2 = dtype == VSR_BF16, dgrad = mode >= 2;
+    const bool bf16 = dtype == VSR_BF16, dgrad = mode >= 2;
     const int xC = dgrad ? cout : cin, yC = dgrad ? cin : cout, in_step = mode == 1 ? 2 : 1, out_step = mode == 3 ? 2 : 1;
-    if (wpack_elems < (w2 ? vsr_wide2_pack_elems(cout, cin, mode) : vsr_wide_pack_elems(cout, cin, mode))) return VSR_ERR_WORKSPACE;
-    if (!w2 && (max_wg || (long long)N * (out_step == 2 ? 4 : 1) * (yC / 64) > 65535)) return VSR_ERR_UNSUPPORTED;
+    if (wpack_elems < (bf16 ? vsr_wide2_pack_elems(cout, cin, mode) : vsr_wide_pack_elems(cout, cin, mode))) return VSR_ERR_WORKSPACE;
+    if (!bf16 && (max_wg || (long long)N * (out_step == 2 ? 4 : 1) * (yC / 64) > 65535)) return VSR_ERR_UNSUPPORTED;
     const WideCtx c{(hipStream_t)stream, dtype, N, nullptr};
-    if (w2) CK(vsr_launch_pack_wide2(w, wpack, cout, cin, mode, c.st)); else CK(vsr_launch_pack_wide(dtype, w, wpack, cout, cin, mode, c.st));
-    return c.wide(x_pm, xC, H * in_step, W * in_step, in_step, H, W, wpack, w2, bias, y_pm, yC, out_step, act, slope, y_act_pm, res_pm, nullptr, aux_pm, max_wg);
+    if (bf16) CK(vsr_launch_pack_wide2(w, wpack, cout, cin, mode, c.st)); else CK(vsr_launch_pack_wide(dtype, w, wpack, cout, cin, mode, c.st));
+    return c.wide(x_pm, xC, H * in_step, W * in_step, in_step, H, W, wpack, bias, y_pm, yC, out_step, act, slope, y_act_pm, res_pm, nullptr, aux_pm, max_wg);
 }
 
 // WideCtx::wgrad_layer: gw (dyC, xC, 3, 3) (views 1) or (dyC, xC, 4, 4) (views 4) += the weight gradient from dy (N, H, W, dyC) and the

@@ -28,15 +28,15 @@ struct WideCtx {
 
     // y (n, H out_step, W out_step, yC) = epilogue(conv(x (n, Hx, Wx, xC))) over the conv domain (n, H, W): 3x3 stride 1, or the parity
     // views of a 4x4 stride-2 conv (in_step 2), or the four output phases of its data gradient (out_step 2).  wpack: the image of
-    // vsr_launch_pack_wide2 (w2) or vsr_launch_pack_wide.  Epilogue: + bias, act, -> y_act, + res, -> y_pre, * mask(aux), -> y.
+    // vsr_launch_pack_wide2 (bf16) or vsr_launch_pack_wide (fp32).  Epilogue: + bias, act, -> y_act, + res, -> y_pre, * mask(aux), -> y.
     // max_wg: at most so many conv_wide2 workgroups per output column (0: none; the engines leave it 0)
-    int wide(const void* x, int xC, int Hx, int Wx, int in_step, int H, int W, const void* wpack, bool w2, const float* bias, void* y, int yC,
+    int wide(const void* x, int xC, int Hx, int Wx, int in_step, int H, int W, const void* wpack, const float* bias, void* y, int yC,
              int out_step, int act, float slope, void* y_act = nullptr, const void* res = nullptr, void* y_pre = nullptr, const void* aux = nullptr,
              int max_wg = 0) const {
         VsrWideConv c = {};
         c.x = x; c.xC = xC; c.Hx = Hx; c.Wx = Wx; c.in_step = in_step; c.nsl = xC / 64;
         c.N = n; c.H = H; c.W = W; c.bias = bias;
-        if (w2) c.wpack2 = wpack; else c.wpack = wpack;
+        if (dtype == VSR_BF16) c.wpack2 = wpack; else c.wpack = wpack;
         c.y = y; c.yC = yC; c.Hy = H * out_step; c.Wy = W * out_step; c.out_step = out_step; c.ncob = yC / 64;
         c.act = act; c.slope = slope; c.y_act = y_act; c.res = res; c.y_pre = y_pre; c.aux = aux; c.max_wg = max_wg;
         return vsr_launch_conv_wide(dtype, c, st);

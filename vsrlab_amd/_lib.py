@@ -81,6 +81,12 @@ class AxisMlpDesc(ctypes.Structure):
     _fields_ = [("outer", c_longlong), ("D", c_int), ("inner", c_longlong), ("hidden", c_int), ("dtype", c_int), ("residual", c_int)]
 
 
+class Conv3dDesc(ctypes.Structure):
+    """struct VsrConv3dDesc (include/vsrlab_conv3d.h)."""
+    _fields_ = [(k, c_int) for k in ("B", "Cin", "Cout", "T", "H", "W", "taps", "dtype", "act")] + \
+               [("slope", c_float), ("pixel_shuffle", c_int), ("x_stride", c_longlong * 3), ("y_stride", c_longlong * 3)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "vsr_abi_version": (c_int, []),
@@ -257,6 +263,18 @@ MIXER_SIGNATURES = {
 }
 MIXER_EXPORTS = tuple(MIXER_SIGNATURES)
 
+# libvsrlab_conv3d.so (include/vsrlab_conv3d.h): the planar, strided Conv3d of ConvST, PixelShufflePack3D and VRT's Upsample, likewise
+CONV3D_LIB_PATH = os.path.join(_HERE, "lib", "libvsrlab_conv3d.so")
+CONV3D_133, CONV3D_311, CONV3D_333 = 0, 1, 2
+CONV3D_ACT_NONE, CONV3D_ACT_LEAKY = 0, 1
+CONV3D_MAX_C = 256
+CONV3D_SIGNATURES = {
+    "vsr_conv3d_workspace_bytes": (c_size_t, [ctypes.POINTER(Conv3dDesc), c_int]),
+    "vsr_conv3d_fwd": (c_int, [ctypes.POINTER(Conv3dDesc), _P, _P, _P, _P, _P, c_size_t, _P]),
+    "vsr_conv3d_bwd": (c_int, [ctypes.POINTER(Conv3dDesc), _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+CONV3D_EXPORTS = tuple(CONV3D_SIGNATURES)
+
 # One row per library: its path, the signatures of its ABI, and those of its debug hooks, which only a library that VSRLAB_AMD_LIB
 # names (another build of libvsrlab_hip.so, e.g. a parent commit's for an A/B run) may predate.  _loaded: one slot per library.
 _LIBS = {
@@ -266,6 +284,7 @@ _LIBS = {
     "warp_taps": (WARP_TAPS_LIB_PATH, WARP_TAPS_SIGNATURES, {}),
     "losses": (LOSSES_LIB_PATH, LOSSES_SIGNATURES, {}),
     "mixer": (MIXER_LIB_PATH, MIXER_SIGNATURES, {}),
+    "conv3d": (CONV3D_LIB_PATH, CONV3D_SIGNATURES, {}),
 }
 _loaded = {}
 
@@ -319,6 +338,11 @@ def load_losses():
 def load_mixer():
     """libvsrlab_mixer.so."""
     return _load("mixer")
+
+
+def load_conv3d():
+    """libvsrlab_conv3d.so."""
+    return _load("conv3d")
 
 
 def check(status, what):

@@ -18,7 +18,7 @@ def install_as_vsrlab(force: bool = False) -> None:
                 "core.schedulers", "core.losses", "vsr", "vsr.models",
                 "vsr.models.RealBasicVSR", "vsr.models.RealBasicVSR.realbasicvsr", "vsr.models.RealBasicVSR.modules",
                 "vsr.models.RealBasicVSR.modules.basicvsr", "vsr.models.RealBasicVSR.modules.spynet",
-                "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.modules",
+                "vsr.models.RealBasicVSR.modules.unet-discriminator", "vsr.models.VRT", "vsr.models.VRT.vrt", "vsr.models.VRT.modules",
                 "vsr.models.VRT.modules.spynet", "vsr.models.VRT.modules.window_attention", "vsr.models.VRT.modules.tmsa", "vsr.models.VRT.modules.deform_conv",
                 "core.utils", "core.metrics", "core.augmentations", "train_gan", "optical_flow",
                 "optical_flow.models", "optical_flow.models.spynet", "optical_flow.models.raft", "optical_flow.models.raft.raft",

@@ -5,7 +5,8 @@ checkpoints load strictly.  Inside ``BasicVSR`` / ``Spynet`` / ``UNetDiscriminat
 call and these modules are its parameter containers; called on their own they dispatch to the per-layer kernels
 (all differentiable: ``ResidualConv`` through its fused forward/backward function, ``ConvReLU`` and the ``ResidualBlock`` stem through
 ``vsr_conv_layer_fwd`` / ``vsr_conv_layer_bwd``).  ``DeformConv`` / ``DeformBlock`` (:33-80) run their deformable convolution
-in ``vsr_deform_conv_fwd`` / ``_bwd``."""
+in ``vsr_deform_conv_fwd`` / ``_bwd``.  ``ConvST`` / ``ConvSTBlock`` (:105-143) run their ``nn.Conv3d`` layers in ``vsr_conv3d_fwd`` /
+``_bwd`` (``core.conv3d_ops``), on the (b, t, c, h, w) tensor as it lies: no rearrange."""
 import math
 
 import torch
@@ -13,6 +14,7 @@ import torch.nn as nn
 from torch.nn.modules.utils import _pair
 
 from ... import functional as VF
+from ..conv3d_ops import conv3d
 
 
 class _SpectralConv2d(nn.Module):
@@ -142,3 +144,34 @@ class DeformBlock(nn.Module):
 
     def forward(self, x):
         return self.conv_out(self.dcblock(self.conv_in(x)))
+
+
+class ConvST(nn.Module):
+    """A (1,3,3) convolution, then a (3,1,1) one, on (b, t, c, h, w)  (conv.py:105-130).  Two launches; the reference's two
+    ``rearrange`` calls are the strides of the descriptor.  The parameters are the reference's ``nn.Conv3d`` children (``conv_xy``,
+    ``conv_t``, no biases), so initialisation and checkpoints are the reference's."""
+
+    def __init__(self, in_ch, out_ch, kernel_size=(3, 3, 3), stride=(1, 1, 1), padding=(1, 1, 1)):
+        super().__init__()
+        kernel_size, stride, padding = (tuple(int(v) for v in a) for a in (kernel_size, stride, padding))
+        if kernel_size != (3, 3, 3) or stride != (1, 1, 1) or padding != (1, 1, 1):
+            raise NotImplementedError("HIP ConvST: kernel (3,3,3), stride 1, padding k // 2 (the class defaults, what ConvSTBlock and "
+                                      f"PixelShufflePack3D instantiate); got kernel {kernel_size}, stride {stride}, padding {padding}")
+        self.conv_xy = nn.Conv3d(in_ch, out_ch, (1, 3, 3), 1, (0, 1, 1), bias=False)
+        self.conv_t = nn.Conv3d(out_ch, out_ch, (3, 1, 1), 1, (1, 0, 0), bias=False)
+
+    def forward(self, x, pixel_shuffle=0):
+        x = conv3d(x, self.conv_xy.weight, time_major=True)
+        return conv3d(x, self.conv_t.weight, pixel_shuffle=pixel_shuffle, time_major=True)
+
+
+class ConvSTBlock(nn.Module):
+    """Conv3d(3,3,3) with bias, then ``blocks`` x ConvST, on (b, t, c, h, w)  (conv.py:132-143)."""
+
+    def __init__(self, blocks, in_ch, out_ch):
+        super().__init__()
+        self.conv_in = nn.Conv3d(in_ch, out_ch, 3, 1, 1)
+        self.block = nn.Sequential(*[ConvST(out_ch, out_ch) for _ in range(blocks)])
+
+    def forward(self, x):
+        return self.block(conv3d(x, self.conv_in.weight, self.conv_in.bias, time_major=True))

@@ -515,8 +515,8 @@ class PmOutput:
 
 
 def fault_guarded(c: Case, driver, *args):
-    """driver(c, *args), the one fault guard of the four per-launch drivers (this file's, trunk_common's, spynet_common's and
-    wide_common's): a HIP error anywhere in it ends the session, so nothing more is started on a card that has faulted."""
+    """driver(c, *args), the one fault guard of the five per-launch drivers (this file's, trunk_common's, spynet_common's,
+    wide_common's and flow_warp_common's): a HIP error anywhere in it ends the session, so nothing more is started on a card that has faulted."""
     try:
         return driver(c, *args)
     except RuntimeError as e:

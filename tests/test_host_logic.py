@@ -124,7 +124,7 @@ def test_debug_signatures_agree_with_the_hooks_one_declaration():
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
     decls = re.findall(r"\bint\s+(vsr_debug_\w+)\s*\(([^)]*)\)\s*;", text)
     names = [n for n, _ in decls]
-    assert len(names) == len(set(names)) == 38, sorted(n for n in names if names.count(n) > 1)
+    assert len(names) == len(set(names)) == 43, sorted(n for n in names if names.count(n) > 1)
     assert set(names) == set(_lib.DEBUG_SIGNATURES) | set(_lib.OTHER_DEBUG_EXPORTS), set(names) ^ (set(_lib.DEBUG_SIGNATURES) | set(_lib.OTHER_DEBUG_EXPORTS))
 
     def c_class(param):

@@ -209,9 +209,9 @@ def _exported_vsr_symbols(path):
 def test_the_hooks_are_additions_to_an_unchanged_abi():
     """The library's exported `vsr_` symbols, enumerated from its dynamic symbol table: before the hooks it exported 74 -- the 67 of
     include/vsrlab_hip.h (= EXPORTS) and 7 vsr_debug_* entries (OTHER_DEBUG_EXPORTS) -- and now exactly those plus the 7
-    reconstruction-tail hooks (81), the 7 propagation-trunk hooks (88), the 7 SPyNet hooks (95) and the 10 entries of the GAN side's pin
-    (105: seven launch hooks, the discriminator's plan, the grid of a conv_wide2 launch and the setter of its test cap), by name: nothing
-    else, nothing missing.  The ABI number stays."""
+    reconstruction-tail hooks (81), the 7 propagation-trunk hooks (88), the 7 SPyNet hooks (95), the 10 entries of the GAN side's pin
+    (105: seven launch hooks, the discriminator's plan, the grid of a conv_wide2 launch and the setter of its test cap) and the 5
+    flow-warp hooks (110), by name: nothing else, nothing missing.  The ABI number stays."""
     L, lib = _lib()
     import os
     import re
@@ -223,20 +223,21 @@ def test_the_hooks_are_additions_to_an_unchanged_abi():
     spy = {"vsr_debug_spy_" + k for k in ("conv", "dgrad", "wgrad", "prepare", "prepare_bwd", "dres", "planar")}
     wide = {"vsr_debug_wide_" + k for k in ("conv", "wgrad", "up2_fwd", "up2_bwd", "mask", "grid")} | {"vsr_debug_vgg_pool", "vsr_debug_vgg_tap",
                                                                                                          "vsr_debug_disc_plan", "vsr_debug_wide2_set_max_wg"}
+    warp = {"vsr_debug_warp_" + k for k in ("fwd", "scatter", "gather", "flowgrad", "add_cast")}
     assert len(wide) == 10
-    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk | spy | wide and len(tail | trunk | spy | wide) == 31
+    assert len(L.OTHER_DEBUG_EXPORTS) == 7 and set(L.DEBUG_SIGNATURES) == tail | trunk | spy | wide | warp and len(tail | trunk | spy | wide | warp) == 36
     assert not set(L.DEBUG_SIGNATURES) & declared and not set(L.DEBUG_SIGNATURES) & set(L.OTHER_DEBUG_EXPORTS)
     got = _exported_vsr_symbols(L.LIB_PATH)
     before = set(L.EXPORTS) | set(L.OTHER_DEBUG_EXPORTS)
     assert got - set(L.DEBUG_SIGNATURES) == before, (sorted(got - set(L.DEBUG_SIGNATURES) - before), sorted(before - got))
-    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7 + 7 + 10
+    assert got - before == set(L.DEBUG_SIGNATURES) and len(got) == 81 + 7 + 7 + 10 + 5
     for name in L.DEBUG_SIGNATURES:
         assert getattr(lib, name).argtypes == L.DEBUG_SIGNATURES[name][1]
 
 
 def test_hostcheck_program_passes_without_sanitizers(tmp_path):
     """tools/hr_tail_hooks_hostcheck.hip and tools/trunk_hooks_hostcheck.hip (the hooks against stubbed launches; `make hooks_hostcheck`
-    runs both under ASan / UBSan) built plain and run.  The trunk program: every refusal before any pack or launch, and what the accepted
+    runs them, and the SPyNet, wide and flow-warp programs, under ASan / UBSan) built plain and run.  The trunk program: every refusal before any pack or launch, and what the accepted
     calls hand to vsr_launch_conv, vsr_launch_wgrad, vsr_launch_wgrad_reduce and vsr_launch_conv3x3_chain (segment counts, strides, i_off,
     accumulate, layer offsets).  The tail program: every refusal before any pack or launch, every accepted call's ConvArgs as given, and -- the one check of it that
     no GPU test can make -- wgrad_launch() passes a 1- or 2-plane cotangent's plane count on to vsr_launch_last2_wgrad (it used to
@@ -248,7 +249,7 @@ def test_hostcheck_program_passes_without_sanitizers(tmp_path):
     env.setdefault("HIPCC", "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
     r = subprocess.run(["make", "-C", os.path.join(root, "vsrlab_amd", "csrc"), "hooks_hostcheck", "HOSTCHECK_SAN=",
                         f"HOSTCHECK_OUT={tmp_path}/hostcheck"], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "\nhostcheck OK" in "\n" + r.stdout and "trunk hostcheck OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "\nhostcheck OK" in "\n" + r.stdout and "trunk hostcheck OK" in r.stdout and "warp hostcheck OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
 
 def test_hooks_refuse_null_pointers_and_bad_sizes_before_any_launch():

@@ -1,5 +1,5 @@
-// The recording launch layer of the four stand-alone host checks (tools/*_hooks_hostcheck.hip): every vsr_launch_* function that
-// csrc/hr_tail_hooks.hip, trunk_hooks.hip, spynet_hooks.hip or wide_hooks.hip reaches, directly or through recipes.h / wide_recipes.h,
+// The recording launch layer of the five stand-alone host checks (tools/*_hooks_hostcheck.hip): every vsr_launch_* function that
+// csrc/hr_tail_hooks.hip, trunk_hooks.hip, spynet_hooks.hip, wide_hooks.hip or warp_hooks.hip reaches, directly or through recipes.h / wide_recipes.h,
 // is replaced by a stub that records what it was handed and launches nothing.  No HIP call is made, so the programs run under
 // ASan / UBSan on a machine without a GPU.  The hooks are called through csrc/debug_hooks.h, and the size formulas
 // (vsr_wgrad_slab_dims, vsr_wide_pack_elems, vsr_wide2_pack_elems) are the library's own, inline in kernels.h.
@@ -51,7 +51,8 @@ static std::set<std::string> g_ever;
 static const std::set<std::string> g_launchers = {      // the stubs' names: hit() and never() refuse any other (a misspelt one)
     "conv", "sign_bits_c64", "last2_dgrad", "last2_wgrad", "wgrad", "wgrad_reduce", "pack_weights", "conv3x3_chain", "resize_norm", "resize_norm_bwd",
     "avgpool2", "avgpool2_bwd_add", "flow_out", "flow_out_bwd", "add_f32", "prepare", "prepare_bwd", "dres", "conv_wide", "pack_wide2", "pack_wide",
-    "wgrad_pairs", "wgrad_reduce_s2", "up2_fwd", "up2_bwd", "mask", "pool_fwd", "pool_bwd", "tap_l1", "tap_sum"};
+    "wgrad_pairs", "wgrad_reduce_s2", "up2_fwd", "up2_bwd", "mask", "pool_fwd", "pool_bwd", "tap_l1", "tap_sum", "warp_fwd", "warp_bwd",
+    "warp_bwd_gather", "warp_bwd_flow", "add_cast"};
 static const char* hit(const char* launcher) {
     if (!g_launchers.count(launcher)) { std::fprintf(stderr, "hostcheck_launch_layer.h: unlisted launcher %s\n", launcher); std::abort(); }
     g_ever.insert(launcher);
@@ -156,6 +157,25 @@ int vsr_launch_tap_l1(int dtype, const void* s, const void* h, void* g, float sc
 }
 int vsr_launch_tap_sum(const double* partial, double* sums, int N, const int* nb, hipStream_t) {
     g_elt.push_back({hit("tap_sum"), {partial, sums}, {N, nb[0], nb[1], nb[2], nb[3], nb[4]}, 0.f}); return VSR_OK;
+}
+
+// ---- the flow warp's launchers (v: dtype, N, H, W, C, then flow_nstride and border where the launcher has them) ----
+int vsr_launch_warp_fwd(int dtype, const void* in, const float* flow, void* out, int N, int H, int W, int C, long long flow_nstride, hipStream_t, int border) {
+    g_elt.push_back({hit("warp_fwd"), {in, flow, out}, {dtype, N, H, W, C, flow_nstride, border}, 0.f}); return VSR_OK;
+}
+int vsr_launch_warp_bwd(int dtype, const void* dout, const float* flow, float* dacc, int N, int H, int W, int C, long long flow_nstride, hipStream_t, int border) {
+    g_elt.push_back({hit("warp_bwd"), {dout, flow, dacc}, {dtype, N, H, W, C, flow_nstride, border}, 0.f}); return VSR_OK;
+}
+int vsr_launch_warp_bwd_gather(int dtype, const void* dout, const float* flow, const void* dtop, long long* S, int* far_count, void* out, int N, int H, int W, int C,
+                               long long flow_nstride, hipStream_t) {
+    g_elt.push_back({hit("warp_bwd_gather"), {dout, flow, dtop, S, far_count, out}, {dtype, N, H, W, C, flow_nstride}, 0.f}); return VSR_OK;
+}
+int vsr_launch_warp_bwd_flow(int dtype, const void* in, const void* dout, const float* flow, float* dflow, int N, int H, int W, int C, long long flow_nstride,
+                             hipStream_t, int border) {
+    g_elt.push_back({hit("warp_bwd_flow"), {in, dout, flow, dflow}, {dtype, N, H, W, C, flow_nstride, border}, 0.f}); return VSR_OK;
+}
+int vsr_launch_add_cast(int dtype, const void* a, const float* s, void* out, int N, int H, int W, int C, hipStream_t) {
+    g_elt.push_back({hit("add_cast"), {a, s, out}, {dtype, N, H, W, C}, 0.f}); return VSR_OK;
 }
 
 // ---- the checks ----

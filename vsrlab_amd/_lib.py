@@ -161,7 +161,7 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-# Test hooks of csrc/hr_tail_hooks.hip and csrc/trunk_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in
+# Test hooks of csrc/hr_tail_hooks.hip, trunk_hooks.hip, spynet_hooks.hip, wide_hooks.hip and warp_hooks.hip: exported by the library, not part of include/vsrlab_hip.h (so not in
 # EXPORTS, like the other vsr_debug_* entries, whose argument types the tests that call them set by hand).  These fourteen have long
 # mixed int / long long / float / pointer lists and three callers each (a host test, a GPU test, the driver), so their types are stated
 # once, here; load() applies them.  csrc/debug_hooks.h declares every hook once for the compiler, and tests/test_host_logic.py holds
@@ -208,6 +208,12 @@ DEBUG_SIGNATURES = {
     "vsr_debug_disc_plan": (c_int, [ctypes.POINTER(DiscDesc), c_int, _P, c_int]),
     "vsr_debug_wide_grid": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "vsr_debug_wide2_set_max_wg": (c_int, [c_int]),
+    # csrc/warp_hooks.hip (dtype, C first; flow_nstride, a long long, follows the flow pointer)
+    "vsr_debug_warp_fwd": (c_int, [c_int, c_int, _P, _P, _LL, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_warp_scatter": (c_int, [c_int, c_int, _P, _P, _LL, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_warp_gather": (c_int, [c_int, c_int, _P, _P, _LL, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "vsr_debug_warp_flowgrad": (c_int, [c_int, c_int, _P, _P, _P, _LL, _P, c_int, c_int, c_int, c_int, _P]),
+    "vsr_debug_warp_add_cast": (c_int, [c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
 }
 
 # libvsrlab_spatial_corr.so (include/vsrlab_spatial_corr.h): the local correlation, a library of its own -- the symbols that

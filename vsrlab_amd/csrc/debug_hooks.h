@@ -72,6 +72,17 @@ int vsr_debug_vgg_pool(int dtype, int op, const void* a_pm, const void* dp_pm, v
 int vsr_debug_vgg_tap(int dtype, const void* s_pm, void* h_pm, int grad, float scale, double* partial, double* sums, int N, int H, int W, int C, void* stream);
 int vsr_debug_wide_grid(int ncob, int out_step, int N, int H, int W, int max_wg, int num_cus, int* out);
 
+// warp_hooks.hip
+int vsr_debug_warp_fwd(int dtype, int C, const void* in_pm, const float* flow, long long flow_nstride, void* out_pm, int border,
+                       int N, int H, int W, void* stream);
+int vsr_debug_warp_scatter(int dtype, int C, const void* dout_pm, const float* flow, long long flow_nstride, float* dacc, const void* a_pm,
+                           void* out_pm, int border, int N, int H, int W, void* stream);
+int vsr_debug_warp_gather(int dtype, int C, const void* dout_pm, const float* flow, long long flow_nstride, const void* dtop_pm, long long* S,
+                          int* far_count, void* out_pm, int N, int H, int W, void* stream);
+int vsr_debug_warp_flowgrad(int dtype, int C, const void* in_pm, const void* dout_pm, const float* flow, long long flow_nstride, float* dflow,
+                            int border, int N, int H, int W, void* stream);
+int vsr_debug_warp_add_cast(int dtype, int C, const void* a_pm, const float* s, void* out_pm, int N, int H, int W, void* stream);
+
 // disc_engine.hip (beside the plan it reads), conv_wide.hip (beside the launcher whose grid it caps)
 int vsr_debug_disc_plan(const VsrDiscDesc* d, int need_backward, long long* offsets, int count);
 int vsr_debug_wide2_set_max_wg(int max_wg);

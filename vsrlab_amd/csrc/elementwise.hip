@@ -18,11 +18,11 @@ __device__ __forceinline__ float warp_coord(float base, float flow, int dim) {
 
 // The bilinear sample of flow_warp at pixel (x, y): top-left tap (x0, y0) and the weights of its two columns and two rows.
 // padding_mode='border' (grid_sample): the coordinate is clamped to the image; a clamped coordinate has no gradient w.r.t. the flow
-// (ATen clip_coordinates_set_grad).  Two conventions of "was clamped" are in use; they differ exactly where a coordinate lands on the
-// first or last pixel centre:
-//   GRAD_CLOSED  the gradient is kept on 0 <= p <= dim - 1: in_x / in_y                       (warp_bwd_flow_kernel)
-//   GRAD_OPEN    it is zeroed at p <= 0 and at p >= dim - 1, as ATen does: grad_gate_open()    (spynet_prepare_bwd_kernel)
-// and three tap policies:
+// (ATen clip_coordinates_set_grad).  One convention of "was clamped" is in use, ATen's:
+//   GRAD_OPEN    the gradient is zeroed at p <= 0 and at p >= dim - 1: grad_gate_open()    (warp_bwd_flow_kernel in border mode,
+//                spynet_prepare_bwd_kernel)
+// (warp_bwd_flow_kernel used to keep it on the closed interval 0 <= p <= dim - 1, in_x / in_y: with a zero flow the first and last column
+// or row then got a flow gradient where the reference has exactly 0.)  Three tap policies:
 //   TEST   zeros padding: each of the four taps is tested against the image: warp_tap() + TAP_IN_IMAGE
 //   CLAMP  border, forward: the second tap's index is clamped into the image, its weight is then 0     (spynet_prepare_kernel)
 //   SKIP   border, adjoint: a second tap outside the image is skipped                                 (spynet_prepare_bwd_kernel)
@@ -541,8 +541,9 @@ __global__ void warp_bwd_flow_kernel(const T* __restrict__ in, const T* __restri
             }
         }
         float* dp = dflow + (long long)n * flow_nstride + (long long)y * W + x;
-        dp[0] = (W > 1 && s.in_x) ? gx : 0.f;                   // GRAD_CLOSED
-        dp[(long long)H * W] = (H > 1 && s.in_y) ? gy : 0.f;
+        // border mode: GRAD_OPEN (in_x / in_y still zero a NaN position); zeros mode: no gate
+        dp[0] = (W > 1 && s.in_x && (!border || grad_gate_open(s.px, W) != 0.f)) ? gx : 0.f;
+        dp[(long long)H * W] = (H > 1 && s.in_y && (!border || grad_gate_open(s.py, H) != 0.f)) ? gy : 0.f;
     }
 }
 

@@ -34,16 +34,15 @@ int vsr_flow_warp_bwd_ex(int dtype, const void* dout_pm, const float* flow, floa
 // Test hook (not in the header): the engine's GATHER form of the 64-channel zeros-padding warp adjoint on its own -- out = T(dtop + adjoint(dout)),
 // near sources gathered, far ones through the 64-bit fixed-point accumulator S (N*H*W*64 long longs, all zero on entry and exit;
 // far_count: one zeroed int).  tests: against the scatter form above, and that a non-finite far contribution stays non-finite.
+// Both are vsr_debug_warp_gather (warp_hooks.hip) at flow_nstride = 2HW.
 extern "C" int vsr_debug_warp_bwd_gather(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
                                          void* out_pm, int N, int H, int W, void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, 64, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_debug_warp_gather(dtype, 64, dout_pm, flow, (long long)2 * H * W, dtop_pm, S, far_count, out_pm, N, H, W, stream);
 }
 // ... the same at Cc = 16, 32 or 64 channels (S: N*H*W*Cc long longs): the narrow engine's propagation warps
 extern "C" int vsr_debug_warp_bwd_gather_c(int dtype, const void* dout_pm, const float* flow, const void* dtop_pm, long long* S, int* far_count,
                                            void* out_pm, int N, int H, int W, int Cc, void* stream) {
-    if (bad_dtype(dtype) || !dout_pm || !flow || !S || !far_count || !out_pm || bad_dims(N, H, W)) return VSR_ERR_BADARG;
-    return vsr_launch_warp_bwd_gather(dtype, dout_pm, flow, dtop_pm, S, far_count, out_pm, N, H, W, Cc, (long long)2 * H * W, (hipStream_t)stream);
+    return vsr_debug_warp_gather(dtype, Cc, dout_pm, flow, (long long)2 * H * W, dtop_pm, S, far_count, out_pm, N, H, W, stream);
 }
 int vsr_flow_warp_bwd_flow_ex(int dtype, const void* in_pm, const void* dout_pm, const float* flow, float* dflow, int N, int H, int W,
                               int Cc, int padding_mode, void* stream) {

@@ -2,6 +2,7 @@
 adjoint of the bilinear resize behind core.utils.resize, and LossPipeline on both.  Checkers: the fp64 restatement of
 tests/losses_common.py (pinned to the reference's recorded results by tests/test_losses_host.py), torch's CPU F.interpolate under
 autograd, and tests/golden/loss_pipeline.npz."""
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
@@ -95,6 +96,42 @@ def test_l1_value_and_exact_gradient(name, xdt, ydt):
     assert none is None and torch.equal(gy3, gy2)
     with torch.no_grad():
         assert torch.equal(WL1Loss()(xg, yg), v)                  # value only (null gradient pointer): the same bits
+
+
+@pytest.mark.parametrize("kind", ["l1", "mse"])
+@pytest.mark.parametrize("n,aligned", [(n, True) for n in LC.ORDER_SIZES] + [(2051, False)], ids=lambda v: str(v))
+def test_the_value_is_summed_in_the_stated_order(n, aligned, kind):
+    """The contract of csrc/reduce.h, pinned: vsr_pixel_loss_fwd_bwd returns exactly the bits of LC.emulate_pair_loss_order -- the
+    per-lane strided sums, the 64-lane shuffle tree, the PAIRWISE combiner, fp32(1 / n), the partials at stride 256 and the halving
+    tree; the in-order combiner or a running sum over the partials give other bits (tests/test_losses_host.py).  Subtract, abs,
+    multiply and add are all there is to these two values, so numpy fp32 reproduces them exactly.  `aligned=False`: views offset by
+    one element, the scalar path.  Charbonnier (csrc/elementwise.hip) and the gradient norm (csrc/train_step.hip) take the same
+    header functions but have a sqrtf in the value, whose device rounding numpy does not restate: they are covered by the identity of
+    their instruction streams with the spelled-out form (profiles/reduce_header_isa.md) and by their own tests, not by an emulation."""
+    from vsrlab_amd import _lib
+    from vsrlab_amd.functional import _STORAGE_DT, _ptr, _stream
+    dev = _gpu()
+    lib = _lib.load_losses()
+    x, y = LC.order_operands(n)
+    want = torch.from_numpy(np.asarray(LC.emulate_pair_loss_order(x.numpy(), y.numpy(), kind, aligned=aligned)).reshape(()))
+    if aligned:
+        xg, yg = x.to(dev), y.to(dev)
+    else:
+        xg, yg = (torch.cat([t.new_zeros(1), t]).to(dev)[1:] for t in (x, y))
+    assert xg.is_contiguous() and ((xg.data_ptr() | yg.data_ptr()) % 16 == 0) == aligned
+    dx = torch.empty(n + 1, dtype=torch.float32, device=dev)[0 if aligned else 1:][:n]
+    assert (dx.data_ptr() % 16 == 0) == aligned
+    f32 = _STORAGE_DT[torch.float32]
+    got = []
+    for _ in range(2):
+        loss = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        scratch = torch.full((lib.vsr_pixel_loss_scratch_floats(),), float("nan"), dtype=torch.float32, device=dev)
+        _lib.check(lib.vsr_pixel_loss_fwd_bwd({"l1": _lib.LOSS_L1, "mse": _lib.LOSS_MSE}[kind], _ptr(xg), f32, _ptr(yg), f32, _ptr(dx),
+                                              _ptr(loss), _ptr(scratch), n, _stream()), "pixel_loss")
+        got.append(loss.cpu())
+    print(f"order {kind} n={n} aligned={aligned}: entry {float(got[0])!r} emulation {float(want)!r}")
+    assert torch.equal(got[0].view(torch.int32), want.view(torch.int32))
+    assert torch.equal(got[1].view(torch.int32), got[0].view(torch.int32))
 
 
 @pytest.mark.parametrize("xdt,ydt", DTYPES, ids=lambda d: str(d).split(".")[-1])

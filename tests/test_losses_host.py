@@ -1,7 +1,7 @@
 """CPU checks of LossPipeline, WL1Loss, rmse_loss and libvsrlab_losses.so: the library's exports and argument checks (every entry
 refuses bad arguments before it touches the GPU), LossPipeline's bookkeeping with stub losses, the refusals of CPU tensors, and the
-restatement of tests/losses_common.py against the reference's recorded fp64 results (tests/golden/loss_pipeline.npz).  Nothing
-here needs a GPU."""
+restatement of tests/losses_common.py against the reference's recorded fp64 results (tests/golden/loss_pipeline.npz), and the
+numpy restatement of the entry's summation order.  Nothing here needs a GPU."""
 import ctypes
 import os
 import re
@@ -218,6 +218,32 @@ def test_the_restatement_reproduces_the_reference(gold):
             want = gold[f"{tag}__{name}"]
             assert float((g - want).abs().max()) <= 1e-12 * float(want.abs().max()), (tag, name)
         assert torch.equal(x.grad, -y.grad)
+
+
+@pytest.mark.parametrize("kind", ["l1", "mse"])
+def test_the_order_emulation_is_the_sum_and_tells_the_orders_apart(kind):
+    """emulate_pair_loss_order restates the summation order of vsr_pixel_loss_fwd_bwd (csrc/reduce.h) in numpy fp32; the GPU test
+    requires the entry's bits to be its bits.  Here: it is a correct sum, and it is sensitive to what it pins.
+
+    Bound: a term passes through at most K roundings -- its own, `trips * vec` additions in its lane and one for the tail, 6 of the
+    shuffle tree, 2 of the combiner, the scaling, ceil(blocks / 256) strided additions and 8 of the halving tree -- so the result is
+    within (1 + 2^-24)^K - 1 <= 2 K 2^-24 (K 2^-24 << 1) of the exact sum, relative to A = the mean of the terms' magnitudes."""
+    for n in LC.ORDER_SIZES:
+        x, y = (t.numpy() for t in LC.order_operands(n))
+        d = x.astype(np.float64) - y.astype(np.float64)
+        exact = float((np.abs(d) if kind == "l1" else d * d).sum() / n)        # the terms are non-negative: A is the value itself
+        for aligned in (True, False):
+            blocks, vec, trips = LC.pair_loss_launch(n, aligned)
+            K = 1 + trips * vec + 1 + 6 + 2 + 1 + -(-blocks // LC.ORDER_BLOCK) + 8
+            got = LC.emulate_pair_loss_order(x, y, kind, aligned=aligned)
+            assert got.dtype == np.float32 and abs(float(got) - exact) <= 2 * K * 2.0 ** -24 * exact, (n, aligned, float(got), exact)
+    assert LC.pair_loss_launch(2051) == (1, 8, 1) and LC.pair_loss_launch(2051, aligned=False) == (9, 1, 1)
+    assert LC.pair_loss_launch(2107395) == (1024, 8, 2) and LC.pair_loss_launch(12293) == (6, 8, 1)
+    bits = lambda v: np.float32(v).view(np.uint32)
+    x, y = (t.numpy() for t in LC.order_operands(2051))
+    assert bits(LC.emulate_pair_loss_order(x, y, kind, combine="inorder")) != bits(LC.emulate_pair_loss_order(x, y, kind))
+    x, y = (t.numpy() for t in LC.order_operands(2107395))
+    assert bits(LC.emulate_pair_loss_order(x, y, kind, final="inorder")) != bits(LC.emulate_pair_loss_order(x, y, kind))
 
 
 def test_documents_say_what_is_provided():

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const WArgs a) {
     }
 }
 
-// db partials: workgroup (co, part) adds the planes part, part + parts, ... of channel co; a fixed tree inside the workgroup
+// db partials: workgroup (co, part) adds the planes part, part + parts, ... of channel co; the fixed tree of reduce.h (tree_sum256) inside the workgroup
 template <typename T>
 __global__ __launch_bounds__(256) void conv3d_dbias_kernel(const T* __restrict__ dz, float* __restrict__ partial, int Cout, int Tn, i64 planes,
                                                            i64 HW, i64 zsb, i64 zsc, i64 zst) {
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256) void conv3d_dbias_kernel(const T* __restrict__
         const T* p = dz + (pl / Tn) * zsb + (i64)co * zsc + (pl % Tn) * zst;
         for (i64 i = threadIdx.x; i < HW; i += 256) s += to_f(p[i]);
     }
-    red[threadIdx.x] = s;
+    red[threadIdx.x] = s;                                           // spelled out: profiles/reduce_header_isa.md
     __syncthreads();
     for (int k = 128; k > 0; k >>= 1) {
         if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];

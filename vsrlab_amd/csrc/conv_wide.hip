@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "elt.h"
 #include "kernels.h"
+#include "reduce.h"
 #include "debug_hooks.h"
 #include "../../include/vsrlab_hip.h"
 
@@ -760,15 +761,7 @@ __global__ void mask_pm_kernel(const T* __restrict__ g, const T* __restrict__ m,
 // ---- spectral norm (torch/nn/utils/spectral_norm.py: compute_weight, n_power_iterations = 1, eps = 1e-12) ----
 // W: (R, K) row-major = weight_orig.reshape(cout, -1).  One workgroup; R <= 512, K <= 8192: the matrices of a discriminator
 // are a few MB and this runs once per forward, so a single-workgroup two-pass mat-vec is plenty.
-__device__ __forceinline__ float blk_sum(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-    return s;
-}
+// Workgroup sums: reduce.h, the wave sums added in INDEX order (sum_inorder); every thread gets the sum and red is reused.
 __global__ __launch_bounds__(1024) void spectral_norm_kernel(const float* __restrict__ W, float* __restrict__ u, float* __restrict__ v,
                                                              float* __restrict__ Wn, float* __restrict__ sigma_out, int R, int K,
                                                              int training, float eps) {
@@ -786,7 +779,8 @@ __global__ __launch_bounds__(1024) void spectral_norm_kernel(const float* __rest
             v[k] = s;
             part += s * s;
         }
-        const float nv = fmaxf(sqrtf(blk_sum(part, red)), eps);
+        wave_sum(part); wave_heads(part, red, true);
+        const float nv = fmaxf(sqrtf(sum_inorder(red)), eps);
         for (int k = tid; k < K; k += nt) v[k] = v[k] / nv;
         __syncthreads();
         // u = normalize(W v): one wave per row
@@ -794,13 +788,14 @@ __global__ __launch_bounds__(1024) void spectral_norm_kernel(const float* __rest
         for (int r = wave; r < R; r += nw) {
             float s = 0.f;
             for (int k = lane; k < K; k += 64) s += W[(long long)r * K + k] * v[k];
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);       // wave_sum, spelled out: profiles/reduce_header_isa.md
             if (lane == 0) su[r] = s;
         }
         __syncthreads();
         float p2 = 0.f;
         for (int r = tid; r < R; r += nt) p2 += su[r] * su[r];
-        const float nu = fmaxf(sqrtf(blk_sum(p2, red)), eps);
+        wave_sum(p2); wave_heads(p2, red, true);
+        const float nu = fmaxf(sqrtf(sum_inorder(red)), eps);
         for (int r = tid; r < R; r += nt) { su[r] = su[r] / nu; u[r] = su[r]; }
         __syncthreads();
     }
@@ -811,10 +806,11 @@ __global__ __launch_bounds__(1024) void spectral_norm_kernel(const float* __rest
         for (int r = wave; r < R; r += nw) {
             float s = 0.f;
             for (int k = lane; k < K; k += 64) s += W[(long long)r * K + k] * v[k];
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);       // wave_sum, spelled out: profiles/reduce_header_isa.md
             if (lane == 0) part += s * su[r];
         }
-        const float sigma = blk_sum(part, red);
+        wave_sum(part); wave_heads(part, red, true);
+        const float sigma = sum_inorder(red);
         if (tid == 0) sigma_out[0] = sigma;
         const long long n = (long long)R * K;
         for (long long i = tid; i < n; i += nt) Wn[i] = W[i] / sigma;
@@ -845,7 +841,8 @@ __global__ __launch_bounds__(1024) void sn_norm_kernel(float* __restrict__ x, in
     __shared__ float red[16];
     float part = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) part += x[i] * x[i];
-    const float ss = blk_sum(part, red);
+    wave_sum(part); wave_heads(part, red, true);
+    const float ss = sum_inorder(red);
     const float nrm = fmaxf(sqrtf(ss), eps);
     for (int i = threadIdx.x; i < n; i += blockDim.x) x[i] = x[i] / nrm;
     if (sigma_out && threadIdx.x == 0) sigma_out[0] = ss / nrm;          // sum_r (s_r / nrm) s_r
@@ -856,7 +853,7 @@ __global__ void sn_wv_kernel(const float* __restrict__ W, const float* __restric
     if (r >= R) return;
     float s = 0.f;
     for (int k = lane; k < K; k += 64) s += W[(long long)r * K + k] * v[k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);               // wave_sum, spelled out: profiles/reduce_header_isa.md
     if (lane == 0) u[r] = s;
 }
 __global__ void sn_scale_kernel(const float* __restrict__ W, const float* __restrict__ sigma, float* __restrict__ Wn, long long n) {
@@ -868,7 +865,8 @@ __global__ void sn_bwd_dot_kernel(const float* __restrict__ dWn, const float* __
     __shared__ float red[16];
     float part = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) part += dWn[i] * W[i];
-    const float s = blk_sum(part, red);
+    wave_sum(part); wave_heads(part, red, true);
+    const float s = sum_inorder(red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 __global__ void sn_bwd_apply_kernel(const float* __restrict__ dWn, const float* __restrict__ u, const float* __restrict__ v,
@@ -898,7 +896,7 @@ __global__ void bce_logits_kernel(const float* __restrict__ x, float* __restrict
         const float sg = 1.f / (1.f + expf(-v));
         if (dx) dx[i] = scale * (sg - target);
     }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
+    wave_sum(local);
     if ((threadIdx.x & 63) == 0) atomicAdd(loss, local * scale);
 }
 

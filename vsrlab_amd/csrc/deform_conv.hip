@@ -17,6 +17,7 @@
 // launch in a fixed order (bit-identical across runs), as wgrad_mfma.hip does.
 #include "elt.h"
 #include "cl_stage.h"
+#include "reduce.h"
 #include "host.h"
 
 namespace {
@@ -353,7 +354,7 @@ __global__ void deform_wgrad_reduce_kernel(const float* slab, int parts, int Cou
     gw[idx] = s;
 }
 
-// d bias[o] = sum of dY[:, o]: one workgroup per channel, fixed order
+// d bias[o] = sum of dY[:, o]: one workgroup per channel, fixed order (reduce.h)
 __global__ __launch_bounds__(256) void deform_bgrad_kernel(const float* dy, float* gb, int N, int Cout, int HW) {
     __shared__ float red[256];
     const int o = blockIdx.x, t = threadIdx.x;
@@ -362,12 +363,7 @@ __global__ __launch_bounds__(256) void deform_bgrad_kernel(const float* dy, floa
         const float* r = dy + ((long long)n * Cout + o) * HW;
         for (int p = t; p < HW; p += 256) s += r[p];
     }
-    red[t] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
+    tree_sum256(s, red);
     if (t == 0) gb[o] = red[0];
 }
 

@@ -4,6 +4,7 @@
 // accesses on pixel-major tensors, planar fp32 accesses coalesced along x.
 #include "elt.h"
 #include "kernels.h"
+#include "reduce.h"
 
 namespace {
 
@@ -778,9 +779,7 @@ __global__ void pack_multi_kernel(const PackArgs a) {
     else reinterpret_cast<float*>(d.dst)[idx] = v;
 }
 
-// The loss VALUE is summed in a fixed order (per-thread strided sums, wave shuffle tree, one partial per workgroup, then ONE
-// workgroup adds the partials in index order): bit-identical from run to run (round 2 added the workgroup partials with atomicAdd,
-// whose arrival order is not).
+// The loss VALUE is summed in the fixed order of reduce.h (pairwise combiner, then charbonnier_sum_kernel): bit-identical from run to run.
 constexpr int CHARB_BLOCKS = 1024;
 __global__ void charbonnier_grad_kernel(const float* __restrict__ sr, const float* __restrict__ hr, float* __restrict__ dsr,
                                         float* __restrict__ partial, long long n, float eps, float scale, int vec) {
@@ -814,22 +813,11 @@ __global__ void charbonnier_grad_kernel(const float* __restrict__ sr, const floa
         local += r;
         dsr[i] = scale * d / r;
     }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+    wave_sums_to_lds(local, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum4_pairwise(red) * scale;
 }
 __global__ void charbonnier_sum_kernel(const float* __restrict__ partial, int nblocks, float* __restrict__ loss) {
-    __shared__ float red[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nblocks; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0];
+    partials_sum256(partial, nblocks, loss);
 }
 
 }  // namespace

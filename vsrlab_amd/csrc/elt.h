@@ -98,7 +98,8 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float* f)
     reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
 }
 
-// PyTorch upsample_bilinear2d(align_corners=False) source index for scale `inv` = 1/4 (or 1/2: upscale = 2) (basicvsr.py:22)
+// PyTorch upsample_bilinear2d(align_corners=False): the two source taps and the weight of the second for output index d;
+// `inv` = in_size / out_size, any ratio (1/4 and 1/2 in basicvsr.py:22, the resize of compute_loss and its adjoint)
 static __device__ __forceinline__ void bil_src(int d, int in_size, int& i0, int& i1, float& l1, float inv) {
     float s = (d + 0.5f) * inv - 0.5f;
     s = s < 0.f ? 0.f : s;

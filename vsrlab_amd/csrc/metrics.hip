@@ -162,6 +162,7 @@ __global__ __launch_bounds__(MT_THREADS) void metrics_tile_kernel(MetricsArgs a)
         __syncthreads();
     }
 
+    // the order of reduce.h (wave sum, then the wave sums in index order), on two values in lock-step: one barrier serves both
     double ds = ssum, dm = msum;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { ds += __shfl_down(ds, off); dm += __shfl_down(dm, off); }
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(MT_THREADS) void metrics_tile_kernel(MetricsArgs a)
     }
 }
 
-// sums[n] = the `per_image` tile partials of image n, added in an order that depends on per_image alone
+// sums[n] = the `per_image` tile partials of image n, added in an order that depends on per_image alone: per thread at stride
+// MT_THREADS, then the halving tree of reduce.h (tree_sum256) on two values in lock-step
 __global__ __launch_bounds__(MT_THREADS) void metrics_reduce_kernel(const double* partial, double* sums, long long per_image) {
     __shared__ double red[2][MT_THREADS];
     const int tid = threadIdx.x;

@@ -18,6 +18,7 @@
 // buffer of an activation that is no longer needed, so the backward needs no scratch of its own.
 #include <vector>
 #include "elt.h"
+#include "reduce.h"
 #include "wide_recipes.h"
 
 namespace {
@@ -145,16 +146,9 @@ __global__ __launch_bounds__(TAP_NT) void tap_l1_kernel(const T* __restrict__ s,
         acc += (double)part;
         if (g) st8<T>(g + img + i * 8, b);
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
     __shared__ double red[TAP_NT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < TAP_NT / 64; ++w) t += red[w];
-        partial[(long long)n * PMAX + blockIdx.x] = t;
-    }
+    wave_sums_to_lds(acc, red);
+    if (threadIdx.x == 0) partial[(long long)n * PMAX + blockIdx.x] = sum_inorder(red, TAP_NT / 64);      // reduce.h: index order
 }
 
 struct TapSumArgs { int nb[NTAP]; };

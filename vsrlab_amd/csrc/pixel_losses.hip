@@ -5,14 +5,14 @@
 //
 //   pair_loss_kernel:  one pass over x and y, each fp32 or bf16 and read as it lies: the gradient w.r.t. x, in x's dtype, and one
 //                      fp32 partial per workgroup.  HBM streaming: a lane moves 8 consecutive elements per trip, in 16-byte accesses.
-//   pair_sum_kernel:   ONE workgroup adds the partials in index order.  As for Charbonnier (elementwise.hip, above CHARB_BLOCKS) the
-//                      value is summed in a fixed order -- per-thread strided sums, wave shuffle tree, one partial per workgroup,
-//                      then this launch -- and is bit-identical from run to run.  No atomics.
+//   pair_sum_kernel:   ONE workgroup adds the partials: the fixed order of reduce.h (pairwise combiner), as for Charbonnier
+//                      (elementwise.hip).  Bit-identical from run to run, no atomics.
 //   resize_bilinear_bwd_kernel:  the adjoint as a GATHER: a lane owns one element of d in, finds by arithmetic the output rows and
 //                      columns whose taps can include it, and decides which do with the forward's own fp32 expressions.  One owner
 //                      per element, no atomics, bit-identical from run to run; an input pixel that no output samples gets 0.
 #include "elt.h"
 #include "host.h"
+#include "reduce.h"
 #include "../../include/vsrlab_losses.h"
 
 namespace {
@@ -64,39 +64,20 @@ __global__ __launch_bounds__(PL_BLOCK) void pair_loss_kernel(const TX* __restric
             if (dx) dx[i] = (TX)g;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+    wave_sums_to_lds(local, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum4_pairwise(red) * scale;
 }
 
+static_assert(PL_BLOCK == 256, "partials_sum256");
 __global__ __launch_bounds__(PL_BLOCK) void pair_sum_kernel(const float* __restrict__ partial, int nblocks, float* __restrict__ loss) {
-    __shared__ float red[PL_BLOCK];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nblocks; i += PL_BLOCK) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = PL_BLOCK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0];
-}
-
-// the forward's source taps of output index o along one axis (train_step.hip, resize_bilinear_kernel: the SAME fp32 expressions, so
-// that forward and adjoint agree on every tap and weight bit for bit): scale = (float)in / (float)out
-static __device__ __forceinline__ void rs_taps(int o, float scale, int in, int& i0, int& i1, float& l) {
-    float f = scale * ((float)o + 0.5f) - 0.5f;
-    f = f < 0.f ? 0.f : f;
-    i0 = (int)f;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l = f - (float)i0;
+    partials_sum256(partial, nblocks, loss);
 }
 
 // The output indices whose taps can include input index i: the source coordinate f(o) = scale (o + 0.5) - 0.5 is monotone in o and
 // i is a tap iff i - 1 < f < i + 1 (or the clamps put it there), so they are the contiguous range (i - 0.5) / scale - 0.5 < o <
 // (i + 1.5) / scale - 0.5.  Found in fp64 and widened by one on each side: the fp32 f differs from the exact one by less than 1 output
-// step's worth only below RS_MAXDIM, and membership is decided by rs_taps, never by this range.
+// step's worth only below RS_MAXDIM, and membership is decided by bil_src (elt.h: the fp32 expressions that resize_bilinear_kernel of
+// train_step.hip spells out, so forward and adjoint agree on every tap and weight bit for bit), never by this range.
 static __device__ __forceinline__ void rs_range(int i, float scale, int out, int& lo, int& hi) {
     const double s = (double)scale;
     const double a = floor(((double)i - 0.5) / s - 0.5) - 1.0, b = ceil(((double)i + 1.5) / s - 0.5) + 1.0;
@@ -119,7 +100,7 @@ __global__ __launch_bounds__(PL_BLOCK) void resize_bilinear_bwd_kernel(const flo
         float acc = 0.f;
         for (int y = ylo; y <= yhi; ++y) {
             int y0, y1; float ly;
-            rs_taps(y, sy, H, y0, y1, ly);
+            bil_src(y, H, y0, y1, ly, sy);
             if (y0 != Y && y1 != Y) continue;
             // on the last row y1 = y0: both weights land on the same input pixel and both are added
             const float wy = (y0 == Y ? 1.f - ly : 0.f) + (y1 == Y ? ly : 0.f);
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(PL_BLOCK) void resize_bilinear_bwd_kernel(const flo
             float racc = 0.f;
             for (int x = xlo; x <= xhi; ++x) {
                 int x0, x1; float lx;
-                rs_taps(x, sx, W, x0, x1, lx);
+                bil_src(x, W, x0, x1, lx, sx);
                 if (x0 != X && x1 != X) continue;
                 racc += row[x] * ((x0 == X ? 1.f - lx : 0.f) + (x1 == X ? lx : 0.f));
             }

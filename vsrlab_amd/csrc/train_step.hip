@@ -7,21 +7,14 @@
 // reduction launch and clip + Adam is ONE elementwise launch (torch: 254-tensor foreach lists, ~10 launches
 // and a host-side norm stack).  Everything here is HBM-bound: 4 reads + 3 writes of 19.4 MB ~ 25 us.
 #include "kernels.h"
+#include "reduce.h"
 #include "../../include/vsrlab_hip.h"
 
 namespace {
 
 constexpr int OPT_BLOCKS = 1024, OPT_THREADS = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* red) {       // red: 4 floats of LDS; all threads get the sum
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// partial[b] = sum of g[i]^2 over block b's grid-stride slice (fixed order: bitwise reproducible)
+// partial[b] = sum of g[i]^2 over block b's grid-stride slice (fixed order, pairwise combiner: reduce.h)
 __global__ __launch_bounds__(OPT_THREADS) void sumsq_partial_kernel(const float* __restrict__ g, long long n, float* __restrict__ partial) {
     __shared__ float red[4];
     float s = 0.f;
@@ -32,7 +25,8 @@ __global__ __launch_bounds__(OPT_THREADS) void sumsq_partial_kernel(const float*
         s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += v * v; }
-    s = block_sum(s, red);
+    wave_sum(s); wave_heads(s, red, true);
+    s = sum4_pairwise(red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -50,7 +44,8 @@ __global__ __launch_bounds__(OPT_THREADS) void adam_clip_kernel(const AdamArgs a
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < OPT_BLOCKS; i += OPT_THREADS) s += a.partial[i];
-    s = block_sum(s, red);
+    wave_sum(s); wave_heads(s, red, true);
+    s = sum4_pairwise(red);
     const float total = sqrtf(s) * fabsf(a.grad_scale);
     float coef = a.grad_scale;
     if (a.max_norm > 0.f) {
@@ -94,6 +89,9 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ in, float* __re
         const int x = (int)(idx % w);
         const int y = (int)((idx / w) % h);
         const long long pl = idx / ((long long)w * h);
+        // bil_src (elt.h) of y and of x with inv = sy, sx, the two axes interleaved: the adjoint (pixel_losses.hip) calls bil_src and
+        // must agree with these taps bit for bit.  Spelled out because the two calls give this kernel another instruction order
+        // (profiles/reduce_header_isa.md).
         float fy = sy * ((float)y + 0.5f) - 0.5f, fx = sx * ((float)x + 0.5f) - 0.5f;
         fy = fy < 0.f ? 0.f : fy; fx = fx < 0.f ? 0.f : fx;
         const int y0 = (int)fy, x0 = (int)fx;
